@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the MedViLL / CXRBERT pretraining step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline fields + the workload's `config`).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs); the inputs are seeded, so
+two runs with the same arguments start from identical weights and batches.  --full adds everything else below: the secondary
+timings in `config`, `roofline` and `cpu_baseline`.
 
 N = 1 runs in this process.  N > 1 needs one process per GPU: when WORLD_SIZE is not set, this script starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py ...` itself as a CHILD process (before
@@ -13,7 +18,7 @@ HBM: forward, CE(mlm, ignore -100) + CE(itm), backward, HF AdamW, the ITM/MLM ac
 gradient all-reduce.  Workload = BASELINE.json configs[1]: BERT-base (12L/12H/768), L = 512 (36 regions + 476 text),
 bidirectional mask, 16-bit MFMA path, batch 64 per GPU (weak scaling), random-init weights, synthetic inputs.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0; with --full it carries two extra objects:
   roofline     the dominant kernel (the FFN-up MFMA GEMM with its fused epilogue) timed alone with HIP events on its
                stream, against the dense bf16 MFMA peak; `roofline.step` carries the whole step: `frac` = EXECUTED FLOP
                rate / peak, `dense_frac` = SURVEY 8d's dense MFU convention (364.076 GFLOP/sample);
@@ -41,6 +46,35 @@ CONFIGS = {
 
 def flops_fwd_per_sample(H, I, V, D, layers, L, N):
     return 2.0 * N * D * H + layers * (L * (8.0 * H * H + 4.0 * H * I) + 4.0 * L * L * H) + 2.0 * H * H + L * (2.0 * H * H + 2.0 * H * V) + 4.0 * H
+
+
+DUMP_SAMPLE = 1 << 20           # flat-parameter entries written by --dump-outputs (4 MiB per float32 array)
+DUMP_SEED = 20240611
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_sample_index(n, k=DUMP_SAMPLE, seed=DUMP_SEED):
+    """Sorted indices of a fixed, seeded sample of k of the n flat parameters: the same in every run and build of one model."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, arrays):
+    """Write each array as <path>/<name>.npy; float32 / float64 only, 64 MiB at most in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise ValueError(f"--dump-outputs: {k} is {v.dtype}, not float32 / float64")
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return sorted(arrays)
 
 
 def cpu_baseline(cfgname, steps=3):
@@ -252,9 +286,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64, help="per-GPU mini-batch")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary timings (padded / BAR / non-cross / full-length / bf16 operands)")
-    ap.add_argument("--no-kernel-table", action="store_true", help="(internal) skip the stand-alone timing of the other kernel families")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the secondary timings, the stand-alone "
+                    "kernel table with the roofline, and the CPU baseline (the three --no-* options below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as "
+                    "DIR/<name>.npy: the loss / accuracy counters and a fixed, seeded sample of the updated fp32 parameters")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary timings (padded / BAR / non-cross / full-length / bf16 operands)")
+    ap.add_argument("--no-kernel-table", action="store_true", help="(internal) with --full: skip the stand-alone timing of the other kernel families")
     ap.add_argument("--dropin-only", action="store_true", help="(internal) print the drop-in user timings as one JSON line and exit: bench.py runs this "
                     "as a CHILD process, so that the trainer is measured in a process of its own like a user's (in a process that already holds "
                     "other models' streams the trainer's two streams can land on one hardware queue)")
@@ -346,9 +384,23 @@ def main():
             dt = float(t[0])
         return dt / n * 1e3, out
 
+    dump_idx = p_init = None
+    if args.dump_outputs and rank == 0:
+        dump_idx = torch.from_numpy(dump_sample_index(model.engine.n_flat)).to(dev)
+        p_init = model.engine.flat_p.index_select(0, dump_idx)
+
     step.time_exchange = dist_on
     ms_per_step, stats = timed(step, batches, args.warmup, args.steps)
     print(f"[bench] rank {rank}: {ms_per_step:.2f} ms/step", file=sys.stderr, flush=True)
+    if dump_idx is not None:
+        # before anything else runs on the model: the secondary timings of --full go on training it
+        step.sync()
+        p = model.engine.flat_p.index_select(0, dump_idx)
+        names = dump_outputs(args.dump_outputs, {
+            "stats": stats.float().cpu().numpy(),                       # [mlm_nll_sum, n_lab, mlm_correct, itm_nll_sum, B, itm_correct]
+            "params_sample": p.cpu().numpy(),                           # fp32 master weights after the last step, at dump_sample_index
+            "params_change_sample": (p - p_init).cpu().numpy()})        # ... less their initial values (warm-up + timed steps)
+        print(f"[bench] wrote {', '.join(names)} to {args.dump_outputs}", file=sys.stderr, flush=True)
     value = world * B / (ms_per_step / 1e3)
     st = stats.cpu()
     exposed_ms = step.exchange_exposed_ms() if dist_on else 0.0
@@ -358,7 +410,7 @@ def main():
     tq_on = model.engine.S.get("tq") is not None          # last layer's attention ran with the consumed rows as its only queries
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         n2 = max(2, min(args.steps, 5))
         if packed:
             # the same step with padding removal switched off (every padded position computed, like the reference does)
@@ -408,123 +460,130 @@ def main():
                 extras["c5_ms_per_step"], _ = timed(st5, b5, 2, n2)
                 del m5, st5, b5
     if rank == 0:
-        f_fwd = flops_fwd_per_sample(cfg.hidden, cfg.intermediate, cfg.vocab_size, cfg.img_hidden, cfg.layers, L, N)
-        f_step = 3.0 * f_fwd
-        dense = value / world * f_step / 1e12
-        # executed FLOPs: the MLM head runs on the labelled rows only (unlabelled rows have zero loss and gradient), and
-        # with padding removal the encoder runs on the valid rows only (positions after the text [SEP] are invisible to
-        # every valid query in the full / seq2seq families and carry no label)
-        n_lab = float(st[1]) / B
-        Hh, Ii, Vv = cfg.hidden, cfg.intermediate, cfg.vocab_size
+        eng = model.engine
         vls = torch.cat([b_["attn_desc"].host_desc()[:, 2] for b_ in batches]).double() if packed else torch.full((1,), float(L)).double()
         rows_mean = float(vls.mean())
-        f_enc = cfg.layers * (rows_mean * (8.0 * Hh * Hh + 4.0 * Hh * Ii) + 4.0 * float((vls * vls).mean()) * Hh)
-        if step.tail_rows:
-            # the last layer's output projection and FFN run on the consumed rows only (labelled rows + one [CLS] row per sample)
-            f_enc -= (rows_mean - (n_lab + 1.0)) * (2.0 * Hh * Hh + 4.0 * Hh * Ii)
-        if tq_on:
-            # ... and its attention scores / context only for those rows as queries (every row stays a key)
-            f_enc -= 4.0 * (float((vls * vls).mean()) - (n_lab + 1.0) * rows_mean) * Hh
-        f_exec = 3.0 * (2.0 * N * cfg.img_hidden * Hh + f_enc + 2.0 * Hh * Hh + n_lab * (2.0 * Hh * Hh + 2.0 * Hh * Vv) + 4.0 * Hh)
-        executed = value / world * f_exec / 1e12
-        # dominant kernel: the FFN-up GEMM with its fused epilogue (largest single launch of the step; its symbol, the 256x256 ring
-        # kernel, and the persistent weight-gradient kernel each take ~20 % of the step's kernel time: profiles/r03_bench_kernel_stats.txt).
-        # The weight-gradient GEMM is reported beside it: its call is two kernels (split-K partials + reduction), timed together.
-        if os.environ.get("MV_BENCH_NO_KERNELS") == "1":      # (profiles/tools/r05_profile_all.sh: kernel statistics of the STEP alone)
-            print(json.dumps({"metric": "image-text pairs/sec pretraining step, BERT-base seq512", "value": value, "unit": "pairs/s", "n_gpus": world,
-                              "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "note": "MV_BENCH_NO_KERNELS=1: no roofline objects"}), flush=True)
-            return
-        kern = time_kernel_case("ffn1")
-        kern_dw = time_kernel_case("dw")
-        # ... and every other MFMA kernel family of the step, each alone on the step's shapes (profiles/tools/dominant.py): attention (one
-        # layer's forward + dQ + dK/dV) and the ten other GEMM calls of a layer.  `coverage` = their stand-alone times x launches per step
-        # over the measured step (the two streams overlap, so the sum can exceed 1)
-        sys.path.insert(0, os.path.join(ROOT, "profiles", "tools"))
-        import dominant
-        kernels = [kern, kern_dw] + ([] if args.no_kernel_table else [time_kernel_case("attn")] + [time_kernel_case(c_) for c_ in dominant.GEMM_FAMILY])
-        alone_ms = sum(k_["ms_per_step_alone"] for k_ in kernels)
-        eng = model.engine
-        pps = lambda ms: (world * B / (ms / 1e3)) if ms else None
+        config = {"workload": c["name"], "per_gpu_batch": B, "global_batch": B * world, "seq_len": L, "regions": N,
+                  "mask": c["family"], "layers": cfg.layers, "hidden": cfg.hidden, "vocab": cfg.vocab_size,
+                  "parallelism": f"dp{world}", "optimizer": "HF AdamW fused", "dropout": cfg.dropout,
+                  "dropout_realised": {"hidden_state_sites": 6554 / 65536, "attention_probabilities": mv.hip_ops.attn_drop_prob(cfg.dropout)},
+                  "precision": ("16-bit MFMA operands, fp32 accumulate / statistics / master weights / optimizer; forward operands "
+                                "f16-encoded, gradient-product operands " + ("bf16-encoded (every stored activation in both encodings)" if eng.dual
+                                                                            else "f16-encoded under a dynamic loss scale (device-side overflow check, "
+                                                                                 "overflowed steps skipped)")
+                                + "; encoder LayerNorm inputs (residual sums) stored "
+                                + ("f16" if eng.ln_in_16 else "fp32") + " (BERT-base logits " + ("3.8-4.6e-3" if eng.ln_in_16 else "3.2-3.4e-3")
+                                + " max-abs from the reference, tolerance 1e-2; bf16-encoded forward operands give 2.6e-2: "
+                                "profiles/r02_bf16_error.txt)") if eng.fadt == torch.float16
+                  else "16-bit MFMA operands, all bf16-encoded",
+                  "loss_scale": (float(eng.scaler[0]) if eng.scaler is not None else None),
+                  "steps_skipped_by_overflow": (int(eng.scaler[5]) if eng.scaler is not None else None),
+                  "optimizer_steps_applied": (int(eng.scaler[4]) if eng.scaler is not None else None),
+                  "rows": (f"padding removed: encoder on the valid rows only (mean {rows_mean:.1f} of {L} positions per sample; "
+                           "results equal the padded run)") if packed else "padded",
+                  "last_layer": "output projection / FFN / LayerNorms of the last layer on the consumed rows only (labelled rows + "
+                                "[CLS] rows; the other rows' outputs are unused and their gradients exactly zero)"
+                                + ("; its attention takes those rows as the only queries (rows reordered with them first, per-sample query limits)"
+                                   if tq_on else "") if step.tail_rows else "all rows"}
+        if args.full:
+            pps = lambda ms: (world * B / (ms / 1e3)) if ms else None
+            config.update({
+                "padded_ms_per_step": extras.get("padded_ms_per_step"), "padded_pairs_per_s": pps(extras.get("padded_ms_per_step")),
+                "full_length_ms_per_step": extras.get("full_length_ms_per_step"),
+                "full_length_pairs_per_s": pps(extras.get("full_length_ms_per_step")),
+                "bar_mask_ms_per_step": extras.get("bar_ms_per_step"), "bar_mask_pairs_per_s": pps(extras.get("bar_ms_per_step")),
+                "noncross_mask_ms_per_step": extras.get("noncross_ms_per_step"),
+                "noncross_mask_pairs_per_s": pps(extras.get("noncross_ms_per_step")),
+                "c3_mixed_mask_ms_per_step": extras.get("c3_ms_per_step"), "c3_pairs_per_s": pps(extras.get("c3_ms_per_step")),
+                "c5_L768_s2s_ms_per_step": extras.get("c5_ms_per_step"), "c5_pairs_per_s": pps(extras.get("c5_ms_per_step")),
+                # what a user of the reference's own interfaces gets (host-resident 9-tuples with int64 [B,L,L] masks through
+                # CXRBERT_Trainer; CXRBERT.forward + torch cross-entropy + backward at B = 16): see drop_in_user_timings
+                "trainer_hostloader_full_ms_per_step": extras.get("trainer_hostloader_full_ms_per_step"),
+                "trainer_hostloader_bar_ms_per_step": extras.get("trainer_hostloader_bar_ms_per_step"),
+                "dropin_forward_backward_b16_ms": extras.get("dropin_forward_backward_b16_ms"),
+                # ... and with the two CrossEntropyLoss calls replaced by medvill_amd.losses.mlm_itm_loss under model.lazy_logits
+                "dropin_lazy_loss_b16_ms": extras.get("dropin_lazy_loss_b16_ms"), "dropin_lazy_loss_b64_ms": extras.get("dropin_lazy_loss_b64_ms"),
+                "dropin_lazy_loss_labels_in_forward_b64_ms": extras.get("dropin_lazy_loss_labels_in_forward_b64_ms")})
+        config.update({
+            "rccl_ranks": rccl_ranks, "dist_backend": backend, "allreduce_exposed_ms": exposed_ms,
+            # rank 0's view of the gradient exchange: when each bucket's all-reduce was issued / completed relative to the first
+            # bucket's issue, and when the compute stream waited for the rest (None undistributed)
+            "allreduce_timeline": timeline,
+            # GPU_MAX_HW_QUEUES / HSA_ENABLE_IPC_MODE_LEGACY / ... and the NUMA binding AS SEEN BY EVERY RANK
+            "rank_env": rank_env})
+        if args.full:
+            config.update({
+                # the same step as a one-rank RCCL job with every collective issued (child process); at 8 ranks the model of DESIGN.md 7
+                # expects 0.5-0.6 ms of exposed all-reduce (the embeddings bucket) on top
+                "rccl_rehearsal_ms_per_step": extras.get("rccl_rehearsal_ms_per_step"),
+                "rccl_rehearsal_exposed_ms": extras.get("rccl_rehearsal_exposed_ms"),
+                "rccl_rehearsal_timeline": extras.get("rccl_rehearsal_timeline"),
+                "expected_exposed_allreduce_ms_at_8_ranks": "0.5-0.6 (model, DESIGN.md 7; unmeasured)"})
+        config.update({"mlm_loss": float(st[0] / max(float(st[1]), 1.0)), "itm_loss": float(st[3] / max(float(st[4]), 1.0))})
         out = {
             "metric": "image-text pairs/sec pretraining step, BERT-base seq512", "value": value, "unit": "pairs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f16/bf16" if eng.dual else ("f16" if eng.fadt == torch.float16 else "bf16"), "data": "synthetic",
-            "config": {"workload": c["name"], "per_gpu_batch": B, "global_batch": B * world, "seq_len": L, "regions": N,
-                       "mask": c["family"], "layers": cfg.layers, "hidden": cfg.hidden, "vocab": cfg.vocab_size,
-                       "parallelism": f"dp{world}", "optimizer": "HF AdamW fused", "dropout": cfg.dropout,
-                       "dropout_realised": {"hidden_state_sites": 6554 / 65536, "attention_probabilities": mv.hip_ops.attn_drop_prob(cfg.dropout)},
-                       "precision": ("16-bit MFMA operands, fp32 accumulate / statistics / master weights / optimizer; forward operands "
-                                     "f16-encoded, gradient-product operands " + ("bf16-encoded (every stored activation in both encodings)" if eng.dual
-                                                                                 else "f16-encoded under a dynamic loss scale (device-side overflow check, "
-                                                                                      "overflowed steps skipped)")
-                                     + "; encoder LayerNorm inputs (residual sums) stored "
-                                     + ("f16" if eng.ln_in_16 else "fp32") + " (BERT-base logits " + ("3.8-4.6e-3" if eng.ln_in_16 else "3.2-3.4e-3")
-                                     + " max-abs from the reference, tolerance 1e-2; bf16-encoded forward operands give 2.6e-2: "
-                                     "profiles/r02_bf16_error.txt)") if eng.fadt == torch.float16
-                       else "16-bit MFMA operands, all bf16-encoded",
-                       "loss_scale": (float(eng.scaler[0]) if eng.scaler is not None else None),
-                       "steps_skipped_by_overflow": (int(eng.scaler[5]) if eng.scaler is not None else None),
-                       "optimizer_steps_applied": (int(eng.scaler[4]) if eng.scaler is not None else None),
-                       "rows": (f"padding removed: encoder on the valid rows only (mean {rows_mean:.1f} of {L} positions per sample; "
-                                "results equal the padded run)") if packed else "padded",
-                       "last_layer": "output projection / FFN / LayerNorms of the last layer on the consumed rows only (labelled rows + "
-                                     "[CLS] rows; the other rows' outputs are unused and their gradients exactly zero)"
-                                     + ("; its attention takes those rows as the only queries (rows reordered with them first, per-sample query limits)"
-                                        if tq_on else "") if step.tail_rows else "all rows",
-                       "padded_ms_per_step": extras.get("padded_ms_per_step"), "padded_pairs_per_s": pps(extras.get("padded_ms_per_step")),
-                       "full_length_ms_per_step": extras.get("full_length_ms_per_step"),
-                       "full_length_pairs_per_s": pps(extras.get("full_length_ms_per_step")),
-                       "bar_mask_ms_per_step": extras.get("bar_ms_per_step"), "bar_mask_pairs_per_s": pps(extras.get("bar_ms_per_step")),
-                       "noncross_mask_ms_per_step": extras.get("noncross_ms_per_step"),
-                       "noncross_mask_pairs_per_s": pps(extras.get("noncross_ms_per_step")),
-                       "c3_mixed_mask_ms_per_step": extras.get("c3_ms_per_step"), "c3_pairs_per_s": pps(extras.get("c3_ms_per_step")),
-                       "c5_L768_s2s_ms_per_step": extras.get("c5_ms_per_step"), "c5_pairs_per_s": pps(extras.get("c5_ms_per_step")),
-                       # what a user of the reference's own interfaces gets (host-resident 9-tuples with int64 [B,L,L] masks through
-                       # CXRBERT_Trainer; CXRBERT.forward + torch cross-entropy + backward at B = 16): see drop_in_user_timings
-                       "trainer_hostloader_full_ms_per_step": extras.get("trainer_hostloader_full_ms_per_step"),
-                       "trainer_hostloader_bar_ms_per_step": extras.get("trainer_hostloader_bar_ms_per_step"),
-                       "dropin_forward_backward_b16_ms": extras.get("dropin_forward_backward_b16_ms"),
-                       # ... and with the two CrossEntropyLoss calls replaced by medvill_amd.losses.mlm_itm_loss under model.lazy_logits
-                       "dropin_lazy_loss_b16_ms": extras.get("dropin_lazy_loss_b16_ms"), "dropin_lazy_loss_b64_ms": extras.get("dropin_lazy_loss_b64_ms"),
-                       "dropin_lazy_loss_labels_in_forward_b64_ms": extras.get("dropin_lazy_loss_labels_in_forward_b64_ms"),
-                       "rccl_ranks": rccl_ranks, "dist_backend": backend, "allreduce_exposed_ms": exposed_ms,
-                       # rank 0's view of the gradient exchange: when each bucket's all-reduce was issued / completed relative to the first
-                       # bucket's issue, and when the compute stream waited for the rest (None undistributed)
-                       "allreduce_timeline": timeline,
-                       # GPU_MAX_HW_QUEUES / HSA_ENABLE_IPC_MODE_LEGACY / ... and the NUMA binding AS SEEN BY EVERY RANK
-                       "rank_env": rank_env,
-                       # the same step as a one-rank RCCL job with every collective issued (child process); at 8 ranks the model of DESIGN.md 7
-                       # expects 0.5-0.6 ms of exposed all-reduce (the embeddings bucket) on top
-                       "rccl_rehearsal_ms_per_step": extras.get("rccl_rehearsal_ms_per_step"),
-                       "rccl_rehearsal_exposed_ms": extras.get("rccl_rehearsal_exposed_ms"),
-                       "rccl_rehearsal_timeline": extras.get("rccl_rehearsal_timeline"),
-                       "expected_exposed_allreduce_ms_at_8_ranks": "0.5-0.6 (model, DESIGN.md 7; unmeasured)",
-                       "mlm_loss": float(st[0] / max(float(st[1]), 1.0)), "itm_loss": float(st[3] / max(float(st[4]), 1.0))},
+            "config": config,
+        }
+        if args.full:
+            f_fwd = flops_fwd_per_sample(cfg.hidden, cfg.intermediate, cfg.vocab_size, cfg.img_hidden, cfg.layers, L, N)
+            f_step = 3.0 * f_fwd
+            dense = value / world * f_step / 1e12
+            # executed FLOPs: the MLM head runs on the labelled rows only (unlabelled rows have zero loss and gradient), and
+            # with padding removal the encoder runs on the valid rows only (positions after the text [SEP] are invisible to
+            # every valid query in the full / seq2seq families and carry no label)
+            n_lab = float(st[1]) / B
+            Hh, Ii, Vv = cfg.hidden, cfg.intermediate, cfg.vocab_size
+            f_enc = cfg.layers * (rows_mean * (8.0 * Hh * Hh + 4.0 * Hh * Ii) + 4.0 * float((vls * vls).mean()) * Hh)
+            if step.tail_rows:
+                # the last layer's output projection and FFN run on the consumed rows only (labelled rows + one [CLS] row per sample)
+                f_enc -= (rows_mean - (n_lab + 1.0)) * (2.0 * Hh * Hh + 4.0 * Hh * Ii)
+            if tq_on:
+                # ... and its attention scores / context only for those rows as queries (every row stays a key)
+                f_enc -= 4.0 * (float((vls * vls).mean()) - (n_lab + 1.0) * rows_mean) * Hh
+            f_exec = 3.0 * (2.0 * N * cfg.img_hidden * Hh + f_enc + 2.0 * Hh * Hh + n_lab * (2.0 * Hh * Hh + 2.0 * Hh * Vv) + 4.0 * Hh)
+            executed = value / world * f_exec / 1e12
+            # dominant kernel: the FFN-up GEMM with its fused epilogue (largest single launch of the step; its symbol, the 256x256 ring
+            # kernel, and the persistent weight-gradient kernel each take ~20 % of the step's kernel time: profiles/r03_bench_kernel_stats.txt).
+            # The weight-gradient GEMM is reported beside it: its call is two kernels (split-K partials + reduction), timed together.
+            if os.environ.get("MV_BENCH_NO_KERNELS") == "1":      # (profiles/tools/r05_profile_all.sh: kernel statistics of the STEP alone)
+                print(json.dumps({"metric": "image-text pairs/sec pretraining step, BERT-base seq512", "value": value, "unit": "pairs/s", "n_gpus": world,
+                                  "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "note": "MV_BENCH_NO_KERNELS=1: no roofline objects"}), flush=True)
+                return
+            kern = time_kernel_case("ffn1")
+            kern_dw = time_kernel_case("dw")
+            # ... and every other MFMA kernel family of the step, each alone on the step's shapes (profiles/tools/dominant.py): attention (one
+            # layer's forward + dQ + dK/dV) and the ten other GEMM calls of a layer.  `coverage` = their stand-alone times x launches per step
+            # over the measured step (the two streams overlap, so the sum can exceed 1)
+            sys.path.insert(0, os.path.join(ROOT, "profiles", "tools"))
+            import dominant
+            kernels = [kern, kern_dw] + ([] if args.no_kernel_table else [time_kernel_case("attn")] + [time_kernel_case(c_) for c_ in dominant.GEMM_FAMILY])
+            alone_ms = sum(k_["ms_per_step_alone"] for k_ in kernels)
             # dominant kernel (the FFN-up GEMM, largest single share of the step): algorithmic FLOPs per launch / its
             # median duration, HIP events over 200 launches after 50 warm-up launches on its own stream (time_kernel_case); traffic = HBM
             # bytes per launch from the committed rocprofv3 PMC passes of the same kernel and shape (profiles/), not of this run
-            "roofline": {"bound": kern["bound"],
-                         "achieved": kern["tflops"] if kern["bound"] == "mfma" else kern["algorithmic_gb_per_s"],
-                         "peak": PEAK_BF16_TFLOPS if kern["bound"] == "mfma" else HBM_PEAK_GBS,
-                         "unit": "TFLOP/s" if kern["bound"] == "mfma" else "GB/s",
-                         "frac": kern["mfma_frac"] if kern["bound"] == "mfma" else kern["hbm_frac"],
-                         "traffic": kern["hbm_traffic_pmc_bytes"],
-                         # the committed rocprofv3 pass of the same command (same-lease HIP events beside it): frac recomputed from it
-                         "profile": kern["profile"],
-                         "ridge_flop_per_byte": RIDGE_FLOP_PER_BYTE,
-                         "kernel": kern, "weight_gradient_gemm": kern_dw, "attention": kernels[2] if len(kernels) > 2 else None,
-                         "kernels": kernels,
-                         "coverage": {"stand_alone_ms_per_step": alone_ms, "of_step": alone_ms / ms_per_step,
-                                      "note": "sum over the listed kernel families of (stand-alone time x launches per step) / measured step; the last "
-                                              "layer's calls run on fewer rows and the weight-gradient GEMMs overlap the main chain on a second stream"},
-                         "step": {"achieved": executed, "frac": executed / PEAK_BF16_TFLOPS,
-                                  "convention": "EXECUTED FLOPs of the whole step (valid rows, labelled rows) / dense 16-bit MFMA peak",
-                                  "dense_tflops": dense, "dense_frac": dense / PEAK_BF16_TFLOPS, "flop_per_sample_dense": f_step,
-                                  "dense_convention": "dense model FLOPs, backward = 2 x forward (SURVEY 8d), whatever was skipped"}},
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.config)
+            out["roofline"] = {"bound": kern["bound"],
+                               "achieved": kern["tflops"] if kern["bound"] == "mfma" else kern["algorithmic_gb_per_s"],
+                               "peak": PEAK_BF16_TFLOPS if kern["bound"] == "mfma" else HBM_PEAK_GBS,
+                               "unit": "TFLOP/s" if kern["bound"] == "mfma" else "GB/s",
+                               "frac": kern["mfma_frac"] if kern["bound"] == "mfma" else kern["hbm_frac"],
+                               "traffic": kern["hbm_traffic_pmc_bytes"],
+                               # the committed rocprofv3 pass of the same command (HIP events of the same session beside it): frac recomputed from it
+                               "profile": kern["profile"],
+                               "ridge_flop_per_byte": RIDGE_FLOP_PER_BYTE,
+                               "kernel": kern, "weight_gradient_gemm": kern_dw, "attention": kernels[2] if len(kernels) > 2 else None,
+                               "kernels": kernels,
+                               "coverage": {"stand_alone_ms_per_step": alone_ms, "of_step": alone_ms / ms_per_step,
+                                            "note": "sum over the listed kernel families of (stand-alone time x launches per step) / measured step; the last "
+                                                    "layer's calls run on fewer rows and the weight-gradient GEMMs overlap the main chain on a second stream"},
+                               "step": {"achieved": executed, "frac": executed / PEAK_BF16_TFLOPS,
+                                        "convention": "EXECUTED FLOPs of the whole step (valid rows, labelled rows) / dense 16-bit MFMA peak",
+                                        "dense_tflops": dense, "dense_frac": dense / PEAK_BF16_TFLOPS, "flop_per_sample_dense": f_step,
+                                        "dense_convention": "dense model FLOPs, backward = 2 x forward (SURVEY 8d), whatever was skipped"}}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args.config)
         print(json.dumps(out), flush=True)
     if dist_on:
         torch.distributed.barrier()
