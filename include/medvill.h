@@ -425,6 +425,40 @@ int mv_count_nonfinite(const float* x, size_t n, float* counter, void* stream);
 int mv_scaler_update(float* state, int growth_interval, float growth, float backoff, float max_scale, float min_scale,
                      void* stream);
 
+/* ---- report generation (KV-cached decode, csrc/mv_decode.hip) -------------------------------------
+ * Replaces the incremental decoder of the reference's report-generation code
+ * (Downstream_task/report_generation_and_vqa/sc/pytorch_pretrained_bert/model.py:1132-1487, driven by generation_decode.py),
+ * which re-projects the whole history at every step.  Here every layer keeps a cache of K / V rows ("slots"); each new query
+ * row lists the slots it sees.  Additive entry points: the pretraining path does not call them.
+ *
+ * mv_gemm_rows: C[M,N] = epi(x[M,K] . W[N,K]^T) for a few rows (M <= 256): the weights are streamed once, 16-bit operands
+ *   (dtype MV_BF16 / MV_F16), f32 accumulation.  epi: MV_EPI_NONE, MV_EPI_BIAS, MV_EPI_BIAS_GELU (C = gelu_erf(x.W^T + bias);
+ *   no pre-activation output) or MV_EPI_BIAS_RES (C = x.W^T + bias + R, R in r_dtype); C in c_dtype (f32 for the LayerNorm
+ *   that follows a residual sum, and for logits).  K % 32 == 0, ldx / ldw multiples of 8, 16-byte aligned x and W.
+ *   Separate from mv_gemm, whose routing is unchanged.
+ * mv_attn_decode: for query row r (q [R, ldq], heads of dh contiguous) and head h:
+ *     ctx[r, h] = sum_j softmax_j( q[r,h] . K[s_j, h] / sqrt(dh) ) V[s_j, h],   s_j = slots[row(r)][j], j < nk[r]
+ *   row(r) = slot_row[r] (int32, nullable: r) -- beams of one sample share a table row prefix, and the MASK row and the token row
+ *   of one beam share one table row with different nk.  K / V caches: [slots, ldkv] in dtype (f32, bf16, f16), f32 softmax.
+ *   max_nk >= every nk[r] (host bound; picks the split count).  dh <= 128, 256 % dh == 0.
+ *   nsplit: 1 = one pass; > 1 = split-KV: the key list is cut in nsplit ranges whose (context, max, sum) partials go to ws
+ *   (>= nsplit * R * A * (dh + 2) floats) and are merged through the log-sum-exp; 0 = the library picks (as many as ws holds).
+ * mv_logprob_topk: per row of logits [R, ld] (f32): lse = log sum exp, logp = x - lse; eos_penalty_id >= 0 sets logp of that
+ *   column to -10000.0 (after the normalisation, as the reference's min_len rule); vals f32 [R,k] / idx int64 [R,k] = the k
+ *   largest logp (k <= 16) in descending order, ties to the lower column.  lse (nullable) f32 [R].  No [R,V] output.
+ * mv_embed_rows: out[r] = LN(E[ids[r]] + Ty[seg[r]] + P[pos[r]]) (HF BertEmbeddings of one token), tables in dtype, gamma /
+ *   beta f32; indices int64, clamped into their tables.                                                                      */
+int mv_gemm_rows(int dtype, int M, int N, int K, const void* x, int ldx, const void* W, int ldw, void* C, int ldc, int c_dtype,
+                 const float* bias, int epi, const void* R, int ldr, int r_dtype, void* stream);
+int mv_attn_decode(int dtype, const void* q, int ldq, const void* k_cache, const void* v_cache, int ldkv, const int32_t* slots,
+                   int ld_slots, const int32_t* slot_row, const int32_t* nk, int max_nk, void* ctx, int ldo, int R, int A, int dh,
+                   int nsplit, float* ws, size_t ws_bytes, void* stream);
+int mv_logprob_topk(const float* logits, int ld, int R, int V, int k, int eos_penalty_id, float* vals, int64_t* idx, float* lse,
+                    void* stream);
+int mv_embed_rows(int dtype, const int64_t* ids, const int64_t* pos, const int64_t* seg, const void* E, const void* P, const void* Ty,
+                  const float* gamma, const float* beta, void* out, int ldo, int R, int H, int V, int maxpos, int ntype, float eps,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

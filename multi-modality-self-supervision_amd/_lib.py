@@ -75,6 +75,11 @@ PROTOTYPES = {
     "mv_adamw_step": [vp, vp, vp, vp, vp, vp, sz, f32, f32, f32, f32, f32, i32, i32, f32, vp, vp],
     "mv_count_nonfinite": [vp, sz, vp, vp],
     "mv_scaler_update": [vp, i32, f32, f32, f32, f32, vp],
+    # report generation (csrc/mv_decode.hip)
+    "mv_gemm_rows": [i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp, i32, vp, i32, i32, vp],
+    "mv_attn_decode": [i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, sz, vp],
+    "mv_logprob_topk": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "mv_embed_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp],
 }
 # include/medvill_debug.h: exported by libmedvill_hip_dbg.so only
 DEBUG_PROTOTYPES = {"mv_debug_set_knob": [i32, i32], "mv_debug_get_knob": [i32]}

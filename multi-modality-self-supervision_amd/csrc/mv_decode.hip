@@ -1,0 +1,424 @@
+// Report-generation decode path (KV-cached, UniLM scheme; DESIGN.md "Generation"): the kernels of one decode step that the
+// pretraining kernels do not cover -- a weight-streaming GEMM for a few rows, attention of a few new queries against a slot
+// cache, the fused log-softmax + top-k of the MLM head's rows and the embedding of single token rows.
+//
+//   mv_gemm_rows     y[M,N] = epi(x[M,K] . W[N,K]^T), M <= 256, 16-bit operands, MFMA 16x16x32, f32 accumulation
+//   mv_attn_decode   ctx[r, head] = softmax(q k^T / sqrt(dh)) v over the cache slots listed for query row r; split-KV + lse merge
+//   mv_logprob_topk  row log-softmax (f32) and its top-k (k <= 16, ties to the lower index), optional EOS column := -10000
+//   mv_embed_rows    x[r] = LN(E[id] + Ty[seg] + P[pos])  (HF BertEmbeddings for one token row)
+#include "mv_common.h"
+#include "mv_gemm_common.h"
+
+// ------------------------------------------------------------------------------------------------ mv_gemm_rows
+// Block = 4 waves = one strip of 16 output columns (16 weight rows) over all M rows.  The 4 waves split the contraction in four
+// contiguous ranges; each wave streams its 16 weight rows straight into VGPRs (the weights are read once, nothing is shared
+// across waves: no LDS round trip) and multiplies every 16-row tile of x against them (x is small and L2-resident).  The four
+// partial [M x 16] tiles are summed through LDS and the epilogue runs on the sum.  Lane l of a 16x16x32 MFMA holds operand row
+// l & 15, k-chunk l >> 4 (8 values); the result lane holds D[4*(l>>4) + i][l & 15] with D rows from the first operand (weights,
+// n) and columns from the second (x, m) -- the layout mv_gemm.hip's tile kernel relies on.
+#define GR_WAVES 4
+#define GR_BN 16
+#define GR_LDR 16      // LDS row stride (floats) of the partial tiles: at M = 256 the four of them fill 64 KiB
+
+template <bool F16, int MT, int CT>
+__global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ W, int ldw,
+                                                       void* __restrict__ c, int ldc, const float* __restrict__ bias, int epi,
+                                                       const void* __restrict__ r, int ldr, int r_dtype, int M, int N, int K) {
+  extern __shared__ float red[];               // [GR_WAVES][MT*16][GR_LDR]
+  const int tid = threadIdx.x, wid = tid >> 6, lane = tid & 63;
+  const int l15 = lane & 15, lq = lane >> 4;
+  const int n0 = blockIdx.x * GR_BN;
+  const int nsteps = K >> 5;                   // K % 32 == 0 (checked by the host)
+  const int s0 = wid * nsteps / GR_WAVES, s1 = (wid + 1) * nsteps / GR_WAVES;
+  const int nrow = min(n0 + l15, N - 1);       // rows past N read row N-1 (in bounds); their columns are never stored
+  const bf16_t* wp = W + (size_t)nrow * ldw + lq * 8;
+  const bf16_t* xp[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) xp[t] = x + (size_t)min(t * 16 + l15, M - 1) * ldx + lq * 8;
+  f32x4 acc[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  constexpr int U = 4;                         // weight fragments in flight per wave
+  int s = s0;
+  for (; s + U <= s1; s += U) {
+    bf16x8 wf[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) wf[u] = __builtin_nontemporal_load((const bf16x8*)(wp + (size_t)(s + u) * 32));
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        const bf16x8 xf = *(const bf16x8*)(xp[t] + (size_t)(s + u) * 32);
+        acc[t] = mma16<F16>(wf[u], xf, acc[t]);
+      }
+    }
+  }
+  for (; s < s1; ++s) {
+    const bf16x8 wf = __builtin_nontemporal_load((const bf16x8*)(wp + (size_t)s * 32));
+#pragma unroll
+    for (int t = 0; t < MT; ++t) acc[t] = mma16<F16>(wf, *(const bf16x8*)(xp[t] + (size_t)s * 32), acc[t]);
+  }
+  // partial tile of this wave: D[n = 4*lq + i][m = t*16 + l15] -> red[wid][m][n]
+  float* mine = red + (size_t)wid * (MT * 16) * GR_LDR;
+#pragma unroll
+  for (int t = 0; t < MT; ++t) *(f32x4*)(mine + (t * 16 + l15) * GR_LDR + 4 * lq) = acc[t];
+  __syncthreads();
+  // epilogue: thread -> (m, 4 consecutive columns)
+  for (int g = tid; g < MT * 16 * 4; g += 256) {
+    const int m = g >> 2, nl = (g & 3) * 4, n = n0 + nl;
+    if (m >= M || n >= N) continue;
+    f32x4 v = *(const f32x4*)(red + m * GR_LDR + nl);
+#pragma unroll
+    for (int w = 1; w < GR_WAVES; ++w) v += *(const f32x4*)(red + ((size_t)w * MT * 16 + m) * GR_LDR + nl);
+    const int nv = min(4, N - n);
+    for (int i = 0; i < nv; ++i) {
+      float o = v[i];
+      if (epi != MV_EPI_NONE) o += bias[n + i];
+      if (epi == MV_EPI_BIAS_GELU) o = gelu_erf(o);
+      else if (epi == MV_EPI_BIAS_RES) o += ld_any(r, (size_t)m * ldr + n + i, r_dtype);
+      v[i] = o;
+    }
+    if (CT == MV_F32) {
+      float* cp = (float*)c + (size_t)m * ldc + n;
+      if (nv == 4 && ((((uintptr_t)cp) & 15) == 0)) *(f32x4*)cp = v;
+      else for (int i = 0; i < nv; ++i) cp[i] = v[i];
+    } else if (CT == MV_F16) {
+      f16_t* cp = (f16_t*)c + (size_t)m * ldc + n;
+      if (nv == 4 && ((((uintptr_t)cp) & 7) == 0)) st4<f16_t>(cp, v);
+      else for (int i = 0; i < nv; ++i) cp[i] = (f16_t)v[i];
+    } else {
+      bf16_t* cp = (bf16_t*)c + (size_t)m * ldc + n;
+      if (nv == 4 && ((((uintptr_t)cp) & 7) == 0)) st4<bf16_t>(cp, v);
+      else for (int i = 0; i < nv; ++i) cp[i] = (bf16_t)v[i];
+    }
+  }
+}
+
+template <bool F16, int MT>
+static void launch_gemm_rows_ct(int c_dtype, dim3 grid, size_t lds, hipStream_t st, const bf16_t* x, int ldx, const bf16_t* W, int ldw,
+                                void* c, int ldc, const float* bias, int epi, const void* r, int ldr, int r_dtype, int M, int N, int K) {
+  if (c_dtype == MV_F32)
+    hipLaunchKernelGGL((gemm_rows_kernel<F16, MT, MV_F32>), grid, dim3(256), lds, st, x, ldx, W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K);
+  else if (c_dtype == MV_F16)
+    hipLaunchKernelGGL((gemm_rows_kernel<F16, MT, MV_F16>), grid, dim3(256), lds, st, x, ldx, W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K);
+  else
+    hipLaunchKernelGGL((gemm_rows_kernel<F16, MT, MV_BF16>), grid, dim3(256), lds, st, x, ldx, W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K);
+}
+
+template <bool F16>
+static void launch_gemm_rows(int mt, int c_dtype, dim3 grid, hipStream_t st, const bf16_t* x, int ldx, const bf16_t* W, int ldw, void* c,
+                             int ldc, const float* bias, int epi, const void* r, int ldr, int r_dtype, int M, int N, int K) {
+  const size_t lds = (size_t)GR_WAVES * mt * 16 * GR_LDR * sizeof(float);
+#define GR_CASE(T_) \
+  case T_: launch_gemm_rows_ct<F16, T_>(c_dtype, grid, lds, st, x, ldx, W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K); break;
+  switch (mt) {
+    GR_CASE(1) GR_CASE(2) GR_CASE(3) GR_CASE(4) GR_CASE(5) GR_CASE(6) GR_CASE(7) GR_CASE(8)
+    GR_CASE(9) GR_CASE(10) GR_CASE(11) GR_CASE(12) GR_CASE(13) GR_CASE(14) GR_CASE(15) GR_CASE(16)
+  }
+#undef GR_CASE
+}
+
+extern "C" int mv_gemm_rows(int dtype, int M, int N, int K, const void* x, int ldx, const void* W, int ldw, void* c, int ldc, int c_dtype,
+                            const float* bias, int epi, const void* r, int ldr, int r_dtype, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!x || !W || !c || M <= 0 || N <= 0 || K <= 0) return MV_E_ARG;
+  if (!mv_is16(dtype) || !mv_dtype_ok(c_dtype)) return MV_E_DTYPE;
+  if (epi != MV_EPI_NONE && epi != MV_EPI_BIAS && epi != MV_EPI_BIAS_GELU && epi != MV_EPI_BIAS_RES) return MV_E_ARG;
+  if (epi != MV_EPI_NONE && !bias) return MV_E_ARG;
+  if (epi == MV_EPI_BIAS_RES && (!r || !mv_dtype_ok(r_dtype) || ldr < N)) return MV_E_ARG;
+  if (M > 256 || (K & 31) || (ldx & 7) || (ldw & 7) || ldx < K || ldw < K || ldc < N) return MV_E_SHAPE;
+  if ((((uintptr_t)x) & 15) || (((uintptr_t)W) & 15)) return MV_E_SHAPE;
+  const int mt = (M + 15) / 16;
+  dim3 grid((N + GR_BN - 1) / GR_BN);
+  if (dtype == MV_F16)
+    launch_gemm_rows<true>(mt, c_dtype, grid, stream, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K);
+  else
+    launch_gemm_rows<false>(mt, c_dtype, grid, stream, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K);
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mv_attn_decode
+// Block = (query row r, head h, split s): 256 threads walk the split's share of the row's key list in tiles of 256 keys -- one
+// key per thread for the score (q . k, f32), an online softmax over the tiles (running max / sum), then the tile's p.V with
+// thread -> (key group g, column d): consecutive lanes read consecutive columns of one value row.  One split writes the
+// normalised context; several write (unnormalised context, max, sum) partials that attn_decode_merge combines (flash-decoding).
+template <typename T>
+__device__ __forceinline__ float dot_row(const float* __restrict__ qs, const T* __restrict__ kr, int dh) {
+  float s = 0.f;
+  for (int d = 0; d < dh; d += 4) {
+    const f32x4 k4 = ld4<T>(kr + d);
+    s += qs[d] * k4[0] + qs[d + 1] * k4[1] + qs[d + 2] * k4[2] + qs[d + 3] * k4[3];
+  }
+  return s;
+}
+
+__device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
+  v = is_max ? wave_max(v) : wave_sum(v);
+  const int wid = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[wid] = v;
+  __syncthreads();
+  float o = sh[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) o = is_max ? fmaxf(o, sh[w]) : o + sh[w];
+  return o;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ kc, const T* __restrict__ vc,
+                                                         int ldkv, const int32_t* __restrict__ slots, int ld_slots,
+                                                         const int32_t* __restrict__ slot_row, const int32_t* __restrict__ nk,
+                                                         T* __restrict__ ctx, int ldo, float* __restrict__ ws, int A, int dh, int nsplit,
+                                                         float scale) {
+  __shared__ float qs[128];
+  __shared__ float ps[256];
+  __shared__ int ss[256];
+  __shared__ float sh[4];
+  __shared__ float red[256];
+  const int tid = threadIdx.x;
+  const int r = blockIdx.x / A, h = blockIdx.x - r * A, sp = blockIdx.y;
+  const int n = nk[r];
+  const int chunk = (n + nsplit - 1) / nsplit;
+  const int j0 = sp * chunk, j1 = min(n, j0 + chunk);
+  const int32_t* sl = slots + (size_t)(slot_row ? slot_row[r] : r) * ld_slots;
+  if (tid < dh) qs[tid] = ldf<T>(q + (size_t)r * ldq + h * dh + tid) * scale;
+  const int G = 256 / dh, g = tid / dh, d = tid - g * dh;
+  float m_run = -INFINITY, l_run = 0.f, acc = 0.f;
+  __syncthreads();
+  for (int jt = j0; jt < j1; jt += 256) {
+    const int j = jt + tid;
+    float sc = -INFINITY;
+    int slot = 0;
+    if (j < j1) {
+      slot = sl[j];
+      sc = dot_row<T>(qs, kc + (size_t)slot * ldkv + h * dh, dh);
+    }
+    const float tmax = block_reduce(sc, sh, true);
+    const float m_new = fmaxf(m_run, tmax);
+    const float p = (j < j1) ? __expf(sc - m_new) : 0.f;
+    ps[tid] = p;
+    ss[tid] = slot;
+    const float tsum = block_reduce(p, sh, false);      // (its barriers also publish ps / ss)
+    const float corr = __expf(m_run - m_new);            // m_run = -inf on the first tile: 0
+    l_run = l_run * corr + tsum;
+    acc *= corr;
+    m_run = m_new;
+    const int cnt = min(256, j1 - jt);
+    const T* vcol = vc + h * dh + d;
+    for (int jj = g; jj < cnt; jj += G) acc += ps[jj] * ldf<T>(vcol + (size_t)ss[jj] * ldkv);
+    __syncthreads();                                     // ps / ss are rewritten by the next tile
+  }
+  red[tid] = acc;
+  __syncthreads();
+  if (tid < dh) {
+    float o = 0.f;
+    for (int k = 0; k < G; ++k) o += red[k * dh + tid];
+    if (nsplit == 1) {
+      stf<T>(ctx + (size_t)r * ldo + h * dh + tid, l_run > 0.f ? o / l_run : 0.f);
+    } else {
+      float* w = ws + ((size_t)blockIdx.x * nsplit + sp) * (dh + 2);
+      w[2 + tid] = o;
+      if (tid == 0) { w[0] = m_run; w[1] = l_run; }
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(128) void attn_decode_merge(const float* __restrict__ ws, T* __restrict__ ctx, int ldo, int A, int dh, int nsplit) {
+  const int rh = blockIdx.x, r = rh / A, h = rh - r * A, d = threadIdx.x;
+  if (d >= dh) return;
+  const float* w = ws + (size_t)rh * nsplit * (dh + 2);
+  float M = -INFINITY;
+  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, w[(size_t)s * (dh + 2)]);
+  float l = 0.f, o = 0.f;
+  if (M > -INFINITY) {
+    for (int s = 0; s < nsplit; ++s) {
+      const float* ws_ = w + (size_t)s * (dh + 2);
+      const float e = __expf(ws_[0] - M);               // an empty split (max -inf) weighs 0
+      l += ws_[1] * e;
+      o += ws_[2 + d] * e;
+    }
+  }
+  stf<T>(ctx + (size_t)r * ldo + h * dh + d, l > 0.f ? o / l : 0.f);
+}
+
+// split count when the caller leaves it to the library: enough (row, head, split) blocks for two per CU, at least 128 keys per
+// split, as many as the workspace holds
+static int decode_splits(int R, int A, int dh, int max_nk, size_t ws_floats) {
+  const int pairs = R * A;
+  int s = (512 + pairs - 1) / pairs;
+  s = min(s, max(1, (max_nk + 127) / 128));
+  s = min(s, 32);
+  while (s > 1 && (size_t)s * pairs * (dh + 2) > ws_floats) --s;
+  return max(s, 1);
+}
+
+extern "C" int mv_attn_decode(int dtype, const void* q, int ldq, const void* k_cache, const void* v_cache, int ldkv, const int32_t* slots,
+                              int ld_slots, const int32_t* slot_row, const int32_t* nk, int max_nk, void* ctx, int ldo, int R, int A, int dh,
+                              int nsplit, float* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!q || !k_cache || !v_cache || !slots || !nk || !ctx || R <= 0 || A <= 0 || dh <= 0 || max_nk <= 0 || nsplit < 0) return MV_E_ARG;
+  if (!mv_dtype_ok(dtype)) return MV_E_DTYPE;
+  if (dh > 128 || (256 % dh) || (dh & 3) || (ldq & 3) || (ldkv & 3) || ldq < A * dh || ldkv < A * dh || ldo < A * dh || ld_slots < 1)
+    return MV_E_SHAPE;
+  const size_t ws_floats = ws ? ws_bytes / sizeof(float) : 0;
+  int ns = nsplit == 0 ? decode_splits(R, A, dh, max_nk, ws_floats) : nsplit;
+  if (ns > 1 && (size_t)ns * R * A * (dh + 2) > ws_floats) return MV_E_WORKSPACE;
+  const float scale = 1.0f / sqrtf((float)dh);
+  dim3 grid(R * A, ns);
+#define AD_LAUNCH(T_)                                                                                                          \
+  hipLaunchKernelGGL(attn_decode_kernel<T_>, grid, dim3(256), 0, stream, (const T_*)q, ldq, (const T_*)k_cache, (const T_*)v_cache, \
+                     ldkv, slots, ld_slots, slot_row, nk, (T_*)ctx, ldo, ws, A, dh, ns, scale);                                 \
+  MV_CHECK_LAUNCH();                                                                                                          \
+  if (ns > 1) hipLaunchKernelGGL(attn_decode_merge<T_>, dim3(R * A), dim3(128), 0, stream, (const float*)ws, (T_*)ctx, ldo, A, dh, ns);
+  if (dtype == MV_F32) { AD_LAUNCH(float) }
+  else if (dtype == MV_BF16) { AD_LAUNCH(bf16_t) }
+  else { AD_LAUNCH(f16_t) }
+#undef AD_LAUNCH
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mv_logprob_topk
+// Block = one row.  Each thread scans a strided share of the columns once: running (max, sum of exp) for the log-sum-exp and a
+// sorted list of its KM best (value desc, index asc).  The row's top-k is then k rounds of a block-wide argmax over the heads
+// of the lists; the winner pops its head.  The EOS column (when penalised) stays in the log-sum-exp and enters the selection
+// with the log-prob -10000 exactly, as the reference's fill_ after log_softmax.
+__device__ __forceinline__ bool tk_better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
+
+template <int KM>
+__device__ __forceinline__ void tk_insert(float (&v)[KM], int (&ix)[KM], float x, int c) {
+#pragma unroll
+  for (int i = 0; i < KM; ++i) {
+    if (tk_better(x, c, v[i], ix[i])) {
+      const float tv = v[i];
+      const int ti = ix[i];
+      v[i] = x;
+      ix[i] = c;
+      x = tv;
+      c = ti;
+    }
+  }
+}
+
+template <int KM>
+__global__ __launch_bounds__(256) void logprob_topk_kernel(const float* __restrict__ logits, int ld, int V, int k, int eos,
+                                                          float* __restrict__ vals, int64_t* __restrict__ idx, float* __restrict__ lse_out) {
+  __shared__ float shm[4], shs[4], shv[4];
+  __shared__ int shi[4];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const float* x = logits + (size_t)row * ld;
+  float v[KM];
+  int ix[KM];
+#pragma unroll
+  for (int i = 0; i < KM; ++i) { v[i] = -INFINITY; ix[i] = 0x7fffffff; }
+  float m = -INFINITY, s = 0.f;
+  for (int c = tid; c < V; c += 256) {
+    const float xv = x[c];
+    if (xv > m) { s = s * __expf(m - xv) + 1.f; m = xv; }
+    else s += __expf(xv - m);
+    if (c != eos) tk_insert<KM>(v, ix, xv, c);
+  }
+  // log-sum-exp of the row
+  float bm = wave_max(m);
+  if (lane == 0) shm[wid] = bm;
+  __syncthreads();
+  bm = fmaxf(fmaxf(shm[0], shm[1]), fmaxf(shm[2], shm[3]));
+  float bs = wave_sum(m > -INFINITY ? s * __expf(m - bm) : 0.f);
+  if (lane == 0) shs[wid] = bs;
+  __syncthreads();
+  const float lse = bm + __logf(shs[0] + shs[1] + shs[2] + shs[3]);
+  if (eos >= 0 && eos < V && tid == (eos & 255)) tk_insert<KM>(v, ix, -10000.0f + lse, eos);
+  for (int o = 0; o < k; ++o) {
+    float bv = v[0];
+    int bi = ix[0];
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_xor(bv, off);
+      const int oi = __shfl_xor(bi, off);
+      if (tk_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    __syncthreads();
+    if (lane == 0) { shv[wid] = bv; shi[wid] = bi; }
+    __syncthreads();
+    bv = shv[0];
+    bi = shi[0];
+    for (int w = 1; w < 4; ++w)
+      if (tk_better(shv[w], shi[w], bv, bi)) { bv = shv[w]; bi = shi[w]; }
+    if (ix[0] == bi) {                              // the owner pops its head
+#pragma unroll
+      for (int i = 0; i + 1 < KM; ++i) { v[i] = v[i + 1]; ix[i] = ix[i + 1]; }
+      v[KM - 1] = -INFINITY;
+      ix[KM - 1] = 0x7fffffff;
+    }
+    if (tid == 0) {
+      vals[(size_t)row * k + o] = (bi == eos) ? -10000.0f : bv - lse;
+      idx[(size_t)row * k + o] = bi;
+    }
+  }
+  if (lse_out && tid == 0) lse_out[row] = lse;
+}
+
+extern "C" int mv_logprob_topk(const float* logits, int ld, int R, int V, int k, int eos_penalty_id, float* vals, int64_t* idx, float* lse,
+                               void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!logits || !vals || !idx || R <= 0 || V <= 0 || ld < V || k <= 0) return MV_E_ARG;
+  if (k > 16 || k > V) return MV_E_SHAPE;
+  const int eos = (eos_penalty_id >= 0 && eos_penalty_id < V) ? eos_penalty_id : -1;
+  if (k == 1) hipLaunchKernelGGL(logprob_topk_kernel<1>, dim3(R), dim3(256), 0, stream, logits, ld, V, k, eos, vals, idx, lse);
+  else if (k <= 4) hipLaunchKernelGGL(logprob_topk_kernel<4>, dim3(R), dim3(256), 0, stream, logits, ld, V, k, eos, vals, idx, lse);
+  else hipLaunchKernelGGL(logprob_topk_kernel<16>, dim3(R), dim3(256), 0, stream, logits, ld, V, k, eos, vals, idx, lse);
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mv_embed_rows
+// Block = one row: x = LN(E[id] + Ty[seg] + P[pos]) in f32, written in `dtype`.  Indices are clamped into their tables.
+template <typename T>
+__global__ __launch_bounds__(256) void embed_rows_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ pos,
+                                                        const int64_t* __restrict__ seg, const T* __restrict__ E, const T* __restrict__ P,
+                                                        const T* __restrict__ Ty, const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, T* __restrict__ out, int ldo, int H, int V, int maxpos,
+                                                        int ntype, float eps) {
+  __shared__ float sh[4];
+  extern __shared__ float rowv[];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const long long id = min(max(ids[r], (int64_t)0), (int64_t)V - 1);
+  const long long p = min(max(pos[r], (int64_t)0), (int64_t)maxpos - 1);
+  const long long t = min(max(seg[r], (int64_t)0), (int64_t)ntype - 1);
+  float s = 0.f;
+  for (int c = tid; c < H; c += 256) {
+    const float e = ldf<T>(E + id * H + c) + ldf<T>(Ty + t * H + c) + ldf<T>(P + p * H + c);
+    rowv[c] = e;
+    s += e;
+  }
+  const float mean = block_reduce(s, sh, false) / H;
+  float q = 0.f;
+  for (int c = tid; c < H; c += 256) {
+    const float dv = rowv[c] - mean;
+    q += dv * dv;
+  }
+  const float rstd = rsqrtf(block_reduce(q, sh, false) / H + eps);
+  for (int c = tid; c < H; c += 256) stf<T>(out + (size_t)r * ldo + c, (rowv[c] - mean) * rstd * gamma[c] + beta[c]);
+}
+
+extern "C" int mv_embed_rows(int dtype, const int64_t* ids, const int64_t* pos, const int64_t* seg, const void* E, const void* P, const void* Ty,
+                             const float* gamma, const float* beta, void* out, int ldo, int R, int H, int V, int maxpos, int ntype, float eps,
+                             void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ids || !pos || !seg || !E || !P || !Ty || !gamma || !beta || !out || R <= 0 || H <= 0 || V <= 0 || maxpos <= 0 || ntype <= 0)
+    return MV_E_ARG;
+  if (ldo < H || H > 8192) return MV_E_SHAPE;
+  const size_t lds = (size_t)H * sizeof(float);
+  if (dtype == MV_F32)
+    hipLaunchKernelGGL(embed_rows_kernel<float>, dim3(R), dim3(256), lds, stream, ids, pos, seg, (const float*)E, (const float*)P,
+                       (const float*)Ty, gamma, beta, (float*)out, ldo, H, V, maxpos, ntype, eps);
+  else if (dtype == MV_BF16)
+    hipLaunchKernelGGL(embed_rows_kernel<bf16_t>, dim3(R), dim3(256), lds, stream, ids, pos, seg, (const bf16_t*)E, (const bf16_t*)P,
+                       (const bf16_t*)Ty, gamma, beta, (bf16_t*)out, ldo, H, V, maxpos, ntype, eps);
+  else if (dtype == MV_F16)
+    hipLaunchKernelGGL(embed_rows_kernel<f16_t>, dim3(R), dim3(256), lds, stream, ids, pos, seg, (const f16_t*)E, (const f16_t*)P,
+                       (const f16_t*)Ty, gamma, beta, (f16_t*)out, ldo, H, V, maxpos, ntype, eps);
+  else return MV_E_DTYPE;
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}

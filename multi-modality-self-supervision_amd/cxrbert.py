@@ -595,6 +595,23 @@ class CXRBERT(nn.Module):
         """ITM logits [B,2] of enc + itm without the MLM head (the retrieval model's forward), differentiable."""
         return self._run(2, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok)
 
+    def generate(self, cls_tok, input_img, sep_tok, max_len=254, beam_size=1, min_len=0, length_penalty=0.0, eos_id=102, mask_id=103,
+                 forced_ids=None, return_traces=False, forbid_duplicate_ngrams=False, forbid_ignore_set=None):
+        """Report generation with a KV cache (DESIGN.md "Generation"): iterated forward under the seq2seq mask, in eval mode, without
+        gradients; the engine's train / keep-activations state is restored afterwards.
+          cls_tok, sep_tok [B,1]; input_img as forward() takes it (region features + positions, or an image for img_encoder).
+          max_len <= max_position_embeddings (text position t < max_pos); the default 254 = seq_len 253 + [SEP].
+        beam_size 1 (greedy, free-running argmax) -> (ids int64 [B, max_len] with [PAD] after EOS, log-probs f32 [B, max_len]).
+        forced_ids [B, T] (teacher-forced scoring, beam 1): token t is fed at step t + 1 -> (argmax ids [B,T], log-probs of forced_ids
+          [B,T], step logits f32 [B, T, V]); step t's logits equal forward()'s MLM logits at text row t.
+        beam_size K > 1: the reference's beam search (model.py:1239-1467; min_len, additive length_penalty) -> (ids [B, max_len],
+          scores f32 [B]) and, with return_traces, the reference's traces {'pred_seq', 'scores', 'wids', 'ptrs'}.
+        forbid_duplicate_ngrams / forbid_ignore_set need tokenizer words: NotImplementedError."""
+        from .generate import generate
+        return generate(self, cls_tok, input_img, sep_tok, max_len=max_len, beam_size=beam_size, min_len=min_len,
+                        length_penalty=length_penalty, eos_id=eos_id, mask_id=mask_id, forced_ids=forced_ids, return_traces=return_traces,
+                        forbid_duplicate_ngrams=forbid_duplicate_ngrams, forbid_ignore_set=forbid_ignore_set)
+
     # ------------------------------------------------------------------ state dict (reference key names)
     def state_dict(self, *a, **k):
         self.engine.wait_optimizer()

@@ -496,3 +496,68 @@ def set_gemm_variant(force: int = 0, nj: int = 0):
     L.set_knob("gemm_force", int(force) & 0xff)
     L.set_knob("gemm_nj", int(nj))
     L.set_knob("gemm_dbg", int(force) >> 8)
+
+
+# ---------------------------------------------------------------------------------------------- report generation (mv_decode.hip)
+def gemm_rows(x, w, c, *, M, N, K, ldx=None, ldw=None, ldc=None, bias=None, epi=EPI_NONE, r=None, ldr=None):
+    """c[M,N] = epi(x[M,K] . w[N,K]^T) for M <= 256 rows, 16-bit x / w (see mv_gemm_rows); c and r in any of the three encodings."""
+    L.require_cuda(x, w, c, bias, r)
+    if x.dtype != w.dtype:
+        raise TypeError("gemm_rows operands must share a dtype")
+    if bias is not None and bias.dtype != torch.float32:
+        raise TypeError("bias must be f32")
+    ldx = ldx if ldx is not None else K
+    ldw = ldw if ldw is not None else K
+    ldc = ldc if ldc is not None else N
+    ldr = ldr if ldr is not None else N
+    rc = _lib().mv_gemm_rows(L.dt_of(x), M, N, K, L.ptr(x), ldx, L.ptr(w), ldw, L.ptr(c), ldc, L.dt_of(c), L.ptr(bias), epi, L.ptr(r), ldr,
+                             L.dt_of(r) if r is not None else 0, L.stream_ptr())
+    L.check(rc, f"mv_gemm_rows(M={M},N={N},K={K},epi={epi})")
+    return c
+
+
+def attn_decode(q, k_cache, v_cache, slots, nk, ctx, *, R, A, dh, max_nk, ldq=None, ldkv=None, ldo=None, slot_row=None, nsplit=0, ws=None):
+    """ctx[R, A*dh] = attention of the R query rows over the cache slots each lists (see mv_attn_decode).  slots int32 [rows, ld];
+    nk int32 [R]; slot_row int32 [R] or None; ws f32 (split-KV partials) or None."""
+    L.require_cuda(q, k_cache, v_cache, slots, nk, ctx, slot_row, ws)
+    if slots.dtype != torch.int32 or nk.dtype != torch.int32 or (slot_row is not None and slot_row.dtype != torch.int32):
+        raise TypeError("attn_decode: slot tables and counts are int32")
+    if not (q.dtype == k_cache.dtype == v_cache.dtype == ctx.dtype):
+        raise TypeError("attn_decode: q, caches and ctx share a dtype")
+    H = A * dh
+    rc = _lib().mv_attn_decode(L.dt_of(q), L.ptr(q), ldq if ldq is not None else H, L.ptr(k_cache), L.ptr(v_cache),
+                               ldkv if ldkv is not None else H, L.ptr(slots), slots.shape[-1], L.ptr(slot_row), L.ptr(nk), int(max_nk),
+                               L.ptr(ctx), ldo if ldo is not None else H, R, A, dh, int(nsplit), L.ptr(ws),
+                               (ws.numel() * 4) if ws is not None else 0, L.stream_ptr())
+    L.check(rc, f"mv_attn_decode(R={R},A={A},dh={dh},nsplit={nsplit})")
+    return ctx
+
+
+def logprob_topk(logits, k, *, R=None, V=None, ld=None, eos_penalty_id=-1, vals=None, idx=None, lse=None):
+    """(vals f32 [R,k], idx int64 [R,k]) = top-k of log_softmax(logits[:, :V]) with ties to the lower index; eos_penalty_id >= 0 sets
+    that column's log-prob to -10000 first (see mv_logprob_topk)."""
+    L.require_cuda(logits, vals, idx, lse)
+    if logits.dtype != torch.float32:
+        raise TypeError("logprob_topk: f32 logits")
+    R = R if R is not None else logits.shape[0]
+    V = V if V is not None else logits.shape[-1]
+    ld = ld if ld is not None else logits.stride(0)
+    if vals is None:
+        vals = torch.empty((R, k), dtype=torch.float32, device=logits.device)
+    if idx is None:
+        idx = torch.empty((R, k), dtype=torch.int64, device=logits.device)
+    rc = _lib().mv_logprob_topk(L.ptr(logits), ld, R, V, int(k), int(eos_penalty_id), L.ptr(vals), L.ptr(idx), L.ptr(lse), L.stream_ptr())
+    L.check(rc, f"mv_logprob_topk(R={R},V={V},k={k})")
+    return vals, idx
+
+
+def embed_rows(ids, pos, seg, E, P, Ty, gamma, beta, out, *, R, H, V, maxpos, eps, ntype=None, ldo=None):
+    """out[r] = LN(E[ids[r]] + Ty[seg[r]] + P[pos[r]]) (int64 indices; see mv_embed_rows)."""
+    L.require_cuda(ids, pos, seg, E, P, Ty, gamma, beta, out)
+    if ids.dtype != torch.int64 or pos.dtype != torch.int64 or seg.dtype != torch.int64:
+        raise TypeError("embed_rows: int64 ids / positions / segments")
+    rc = _lib().mv_embed_rows(L.dt_of(out), L.ptr(ids), L.ptr(pos), L.ptr(seg), L.ptr(E), L.ptr(P), L.ptr(Ty), L.ptr(gamma), L.ptr(beta),
+                              L.ptr(out), ldo if ldo is not None else H, R, H, V, maxpos, ntype if ntype is not None else Ty.shape[0],
+                              float(eps), L.stream_ptr())
+    L.check(rc, "mv_embed_rows")
+    return out

@@ -47,3 +47,24 @@ class CXRBertForRetrieval(nn.Module):
         else:
             logits = self.forward(cls_tok, input_txt, attn_mask, segment, input_img, sep_tok)
         return torch.softmax(logits.float(), dim=-1)[:, 1]
+
+
+class CXRBertForGeneration(nn.Module):
+    """Report generation from a pretrained CXRBERT (the reference's BertForSeq2SeqDecoder use of it, driven by generation_decode.py):
+    a thin holder whose `generate` is CXRBERT.generate (KV-cached greedy / beam search on the HIP kernels)."""
+
+    def __init__(self, config, args=None, **kw):
+        super().__init__()
+        self.bert = CXRBERT(config, args, **kw)
+
+    @classmethod
+    def from_pretrained(cls, path, args=None, **kw):
+        m = cls.__new__(cls)
+        nn.Module.__init__(m)
+        m.bert = CXRBERT.from_pretrained(path, args=args, **kw)
+        return m
+
+    def generate(self, cls_tok, input_img, sep_tok, **kw):
+        return self.bert.generate(cls_tok, input_img, sep_tok, **kw)
+
+    forward = generate
