@@ -345,8 +345,9 @@ int mv_colsum_partials(const float* part, int P, int ld, int N, float* out, cons
 int mv_add(int dtype, const void* a, const void* b, void* c, size_t n, void* stream);
 
 /* out = dy * gelu_erf'(z) (mode 0; backward of the MLM transform's activation,
- * cxrbert_origin.py:176-181,216) or out = dy * (1 - z*z) (mode 1; tanh backward of the pooler,
- * z holds the tanh OUTPUT).  n elements, n % 4 == 0. */
+ * cxrbert_origin.py:176-181,216), out = dy * (1 - z*z) (mode 1; tanh backward of the pooler,
+ * z holds the tanh OUTPUT) or out = dy * (z > 0) (mode 2; ReLU backward of the VQA answer classifier, z holds the ReLU
+ * OUTPUT).  n elements, n % 4 == 0. */
 int mv_dact(int dtype, int mode, const void* dy, const void* z, void* out, size_t n, void* stream);
 
 /* 2-D cast: dst[r, 0..cols) = src[r, 0..cols), dst[r, cols..ldd) = 0 (pads a [rows, V] gradient
@@ -433,7 +434,8 @@ int mv_scaler_update(float* state, int growth_interval, float growth, float back
  *
  * mv_gemm_rows: C[M,N] = epi(x[M,K] . W[N,K]^T) for a few rows (M <= 256): the weights are streamed once, 16-bit operands
  *   (dtype MV_BF16 / MV_F16), f32 accumulation.  epi: MV_EPI_NONE, MV_EPI_BIAS, MV_EPI_BIAS_GELU (C = gelu_erf(x.W^T + bias);
- *   no pre-activation output) or MV_EPI_BIAS_RES (C = x.W^T + bias + R, R in r_dtype); C in c_dtype (f32 for the LayerNorm
+ *   no pre-activation output), MV_EPI_BIAS_RELU (C = max(x.W^T + bias, 0); the VQA answer classifier) or MV_EPI_BIAS_RES
+ *   (C = x.W^T + bias + R, R in r_dtype); C in c_dtype (f32 for the LayerNorm
  *   that follows a residual sum, and for logits).  K % 32 == 0, ldx / ldw multiples of 8, 16-byte aligned x and W.
  *   Separate from mv_gemm, whose routing is unchanged.
  * mv_attn_decode: for query row r (q [R, ldq], heads of dh contiguous) and head h:
@@ -458,6 +460,28 @@ int mv_logprob_topk(const float* logits, int ld, int R, int V, int k, int eos_pe
 int mv_embed_rows(int dtype, const int64_t* ids, const int64_t* pos, const int64_t* seg, const void* E, const void* P, const void* Ty,
                   const float* gamma, const float* beta, void* out, int ldo, int R, int H, int V, int maxpos, int ntype, float eps,
                   void* stream);
+
+/* ---- VQA fine-tuning and answer prediction (csrc/mv_vqa.hip) --------------------------------------
+ * The answer classifier of the reference's VQA model (Downstream_task/report_generation_and_vqa/sc/pytorch_pretrained_bert/
+ * model.py:939-943,979-983,1016-1041): Linear(H, 2H) + ReLU + Linear(2H, A), nn.BCEWithLogitsLoss over soft targets, the
+ * argmax score split by answer type.  The two products run on mv_gemm_rows / mv_gemm.  Additive entry points.
+ *
+ * mv_bce_fwd_bwd: per row r of logits [R, ld] (f32) and soft targets [R, A] (f32, contiguous; nullable when stats and dgrad are):
+ *     stats[1] += sum_c max(z,0) - z*y + log1p(exp(-|z|))                                      (the loss SUM; mean = / (R*A))
+ *     dgrad[r, c] = (sigmoid(z) - y) * g * S  for c < A, 0 for A <= c < ldd   (d_dtype; g = *grad_scale_dev when non-null, else
+ *                   grad_scale_host; S = *loss_scale_dev when non-null, else 1 -- as mv_ce_fwd_bwd)
+ *     arg_train[r] = argmax_c z (int64), arg_infer[r] = argmax_{c >= 1} z (int64, the column itself: the "+1" is included);
+ *                   ties to the lower column
+ *     stats f32 [6] += {y[arg_train], loss, closed score, closed count, open score, open count}: ans_type int32 [R] (nullable)
+ *                   0 = CLOSED, 1 = OPEN; any other value counts in neither split (zero stats first).
+ *   stats, dgrad, arg_train and arg_infer are each nullable (inference needs neither loss nor gradient).
+ * mv_rows_mul: out[i, :H] = a[rows_a[i], :H] * b[rows_b[i], :H] (dtype; a negative row index gives zeros).  H and the leading
+ *   dimensions multiples of 4, bases aligned to 4 elements.                                                                    */
+int mv_bce_fwd_bwd(const float* logits, int ld, const float* target, const int32_t* ans_type, int R, int A, float* stats,
+                   void* dgrad, int d_dtype, int ldd, const float* grad_scale_dev, float grad_scale_host, const float* loss_scale_dev,
+                   int64_t* arg_train, int64_t* arg_infer, void* stream);
+int mv_rows_mul(int dtype, const void* a, int lda, const int32_t* rows_a, const void* b, int ldb, const int32_t* rows_b, int R, int H,
+                void* out, int ldo, void* stream);
 
 #ifdef __cplusplus
 }

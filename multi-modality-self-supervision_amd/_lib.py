@@ -80,6 +80,9 @@ PROTOTYPES = {
     "mv_attn_decode": [i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, sz, vp],
     "mv_logprob_topk": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "mv_embed_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp],
+    # VQA (csrc/mv_vqa.hip)
+    "mv_bce_fwd_bwd": [vp, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, f32, vp, vp, vp, vp],
+    "mv_rows_mul": [i32, vp, i32, vp, vp, i32, vp, i32, i32, vp, i32, vp],
 }
 # include/medvill_debug.h: exported by libmedvill_hip_dbg.so only
 DEBUG_PROTOTYPES = {"mv_debug_set_knob": [i32, i32], "mv_debug_get_knob": [i32]}

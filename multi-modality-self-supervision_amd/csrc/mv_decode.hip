@@ -75,6 +75,7 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict
       float o = v[i];
       if (epi != MV_EPI_NONE) o += bias[n + i];
       if (epi == MV_EPI_BIAS_GELU) o = gelu_erf(o);
+      else if (epi == MV_EPI_BIAS_RELU) o = fmaxf(o, 0.f);
       else if (epi == MV_EPI_BIAS_RES) o += ld_any(r, (size_t)m * ldr + n + i, r_dtype);
       v[i] = o;
     }
@@ -123,7 +124,8 @@ extern "C" int mv_gemm_rows(int dtype, int M, int N, int K, const void* x, int l
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !W || !c || M <= 0 || N <= 0 || K <= 0) return MV_E_ARG;
   if (!mv_is16(dtype) || !mv_dtype_ok(c_dtype)) return MV_E_DTYPE;
-  if (epi != MV_EPI_NONE && epi != MV_EPI_BIAS && epi != MV_EPI_BIAS_GELU && epi != MV_EPI_BIAS_RES) return MV_E_ARG;
+  if (epi != MV_EPI_NONE && epi != MV_EPI_BIAS && epi != MV_EPI_BIAS_GELU && epi != MV_EPI_BIAS_RES && epi != MV_EPI_BIAS_RELU)
+    return MV_E_ARG;
   if (epi != MV_EPI_NONE && !bias) return MV_E_ARG;
   if (epi == MV_EPI_BIAS_RES && (!r || !mv_dtype_ok(r_dtype) || ldr < N)) return MV_E_ARG;
   if (M > 256 || (K & 31) || (ldx & 7) || (ldw & 7) || ldx < K || ldw < K || ldc < N) return MV_E_SHAPE;

@@ -969,21 +969,22 @@ extern "C" int mv_add(int dtype, const void* a, const void* b, void* c, size_t n
   return MV_OK;
 }
 
-// out = dy * gelu'(z)   (mode 0)   |   out = dy * (1 - y*y)   (mode 1: tanh backward, z holds y)
+// out = dy * gelu'(z)   (mode 0)   |   out = dy * (1 - y*y)   (mode 1: tanh backward, z holds y)   |   out = dy * (y > 0)   (mode 2:
+// ReLU backward, z holds y)
 template <typename T>
 __global__ void dact_kernel(const T* __restrict__ dy, const T* __restrict__ z, T* __restrict__ out, size_t n4, int mode) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
     const f32x4 d = ld4<T>(dy + 4 * i), zz = ld4<T>(z + 4 * i);
     f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = mode == 0 ? d[e] * dgelu_erf(zz[e]) : d[e] * (1.0f - zz[e] * zz[e]);
+    for (int e = 0; e < 4; ++e) o[e] = mode == 0 ? d[e] * dgelu_erf(zz[e]) : mode == 1 ? d[e] * (1.0f - zz[e] * zz[e]) : (zz[e] > 0.f ? d[e] : 0.f);
     st4<T>(out + 4 * i, o);
   }
 }
 extern "C" int mv_dact(int dtype, int mode, const void* dy, const void* z, void* out, size_t n, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!dy || !z || !out || n == 0) return MV_E_ARG;
-  if ((n & 3) || (mode != 0 && mode != 1)) return MV_E_SHAPE;
+  if ((n & 3) || mode < 0 || mode > 2) return MV_E_SHAPE;
   const size_t n4 = n / 4;
   int blocks = (int)((n4 + 255) / 256);
   if (blocks > 2048) blocks = 2048;

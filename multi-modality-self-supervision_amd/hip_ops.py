@@ -561,3 +561,35 @@ def embed_rows(ids, pos, seg, E, P, Ty, gamma, beta, out, *, R, H, V, maxpos, ep
                               float(eps), L.stream_ptr())
     L.check(rc, "mv_embed_rows")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- VQA (mv_vqa.hip)
+def bce_fwd_bwd(logits, A, *, R=None, ld=None, target=None, ans_type=None, stats=None, dgrad=None, ldd=None, grad_scale=1.0,
+                grad_scale_dev=None, loss_scale_dev=None, arg_train=None, arg_infer=None):
+    """BCEWithLogits over soft targets [R, A] (sum into stats[1]), its gradient (padding columns A..ldd zero), the training / inference
+    argmax (int64 [R]) and the score split stats f32[6] (see mv_bce_fwd_bwd).  Every output is optional."""
+    L.require_cuda(logits, target, ans_type, stats, dgrad, grad_scale_dev, loss_scale_dev, arg_train, arg_infer)
+    if logits.dtype != torch.float32 or (target is not None and (target.dtype != torch.float32 or not target.is_contiguous())):
+        raise TypeError("bce_fwd_bwd: f32 logits and contiguous f32 targets")
+    if ans_type is not None and ans_type.dtype != torch.int32:
+        raise TypeError("bce_fwd_bwd: ans_type int32")
+    if any(t is not None and t.dtype != torch.int64 for t in (arg_train, arg_infer)):
+        raise TypeError("bce_fwd_bwd: argmax outputs int64")
+    R = R if R is not None else logits.shape[0]
+    ld = ld if ld is not None else logits.stride(0)
+    ldd = ldd if ldd is not None else (dgrad.stride(0) if dgrad is not None else 0)
+    rc = _lib().mv_bce_fwd_bwd(L.ptr(logits), ld, L.ptr(target), L.ptr(ans_type), R, A, L.ptr(stats), L.ptr(dgrad),
+                               L.dt_of(dgrad) if dgrad is not None else 0, ldd, L.ptr(grad_scale_dev), float(grad_scale),
+                               L.ptr(loss_scale_dev), L.ptr(arg_train), L.ptr(arg_infer), L.stream_ptr())
+    L.check(rc, f"mv_bce_fwd_bwd(R={R},A={A})")
+
+
+def rows_mul(a, rows_a, b, rows_b, out, *, R, H, lda=None, ldb=None, ldo=None):
+    """out[i] = a[rows_a[i]] * b[rows_b[i]] over H columns (int32 row indices; see mv_rows_mul)."""
+    L.require_cuda(a, rows_a, b, rows_b, out)
+    if not (a.dtype == b.dtype == out.dtype) or rows_a.dtype != torch.int32 or rows_b.dtype != torch.int32:
+        raise TypeError("rows_mul: a, b, out share a dtype; int32 row indices")
+    rc = _lib().mv_rows_mul(L.dt_of(a), L.ptr(a), lda if lda is not None else H, L.ptr(rows_a), L.ptr(b), ldb if ldb is not None else H,
+                            L.ptr(rows_b), R, H, L.ptr(out), ldo if ldo is not None else H, L.stream_ptr())
+    L.check(rc, f"mv_rows_mul(R={R},H={H})")
+    return out
