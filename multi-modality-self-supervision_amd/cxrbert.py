@@ -138,11 +138,9 @@ class _CXRBertFn(torch.autograd.Function):
         model = ctx.model
         eng = model.engine
         # gradients a previous backward left in the flat buffer THROUGH the .grad views (no zero_grad in between, or
-        # zero_grad(set_to_none=False)): keep them, this backward adds to them like autograd would
-        if ctx.want_heads == 3 and model._lazy is not None and model._lazy[5]:
-            held = model.__dict__.pop("_held", None)             # set aside by the loss, which has already zeroed the buffer
-        else:
-            held = eng.flat_g.clone() if (_use_views(model) and eng.flat_g is not None and _holds_views(model)) else None
+        # zero_grad(set_to_none=False)): keep them, this backward adds to them like autograd would.  Decided here, when the backward starts:
+        # a zero_grad() between the loss and the backward (the reference's order, train_origin.py:129-131) changes what .grad holds
+        held = eng.flat_g.clone() if (_use_views(model) and eng.flat_g is not None and _holds_views(model)) else None
         _CXRBertFn._backward_once(ctx, g0, g1)
         if eng.scaler is not None:
             # f16 gradient operands under a loss scale: this path hands gradients to torch (an external optimizer), so an
@@ -262,11 +260,11 @@ class _LazyLossFn(torch.autograd.Function):
         eng = model.engine
         R, B = int(rows.numel()), int(aligned.numel())
         # A backward is coming (the handle requires grad): the head runs ONCE, with its gradient for d loss = 1 -- the flat gradient buffer
-        # is zeroed here instead of in the backward (gradients held through .grad views are set aside first, see _CXRBertFn.backward).  The
-        # backward reuses that when it is indeed handed 1.0 and redoes the head otherwise (an upstream factor, a loss-scale retry).
-        pre = bool(ctx.needs_input_grad[0]) and model.grad_in_loss
+        # is zeroed here instead of in the backward.  The backward reuses that when it is indeed handed 1.0 and redoes the head otherwise (an
+        # upstream factor, a loss-scale retry).  Not while .grad holds views of the buffer (a previous backward, no zero_grad() yet): the loss
+        # leaves .grad alone -- a zero_grad() may still come before the backward (train_origin.py:129-131) -- and the backward runs the head
+        pre = bool(ctx.needs_input_grad[0]) and model.grad_in_loss and not (_use_views(model) and eng.flat_g is not None and _holds_views(model))
         if pre:
-            model._held = eng.flat_g.clone() if (_use_views(model) and eng.flat_g is not None and _holds_views(model)) else None
             eng.zero_grad()
         stats = eng.heads_train(rows, ids, aligned, mlm_scale=(1.0 / max(R, 1)) if (mlm_on or not pre) else 0.0,
                                 itm_scale=(1.0 / B) if (itm_on or not pre) else 0.0, compute_grad=pre)
