@@ -25,6 +25,12 @@ Fixtures:
   base_noncross.npz  BERT-base L=512 B=1, non-cross modality mask (config 4; n2 = 38 is not tile-aligned)
   base768_s2s.npz    BERT-base L=768 (100 regions + 665 text, max_position_embeddings 768) B=1, seq2seq (config 5)
 
+  base_bar.npz            BERT-base L=512 B=2 ragged, BAR (the reference's default mask) + gradients of every parameter
+  base_noncross_grad.npz  the same, non-cross (config 4; the pads lie inside the text block) + gradients
+  base_mixed_b4.npz       BERT-base L=512 B=4 ragged, per-sample full / s2s (config 3's batch form; both families drawn) + gradients
+  base768_s2s_grad.npz    BERT-base L=768 B=2 ragged, seq2seq (config 5) + gradients
+  c1_<fam>_grad.npz       config C1 for bar / noncross / 1d with gradients (a seed of their own; no hidden states)
+
     python oracle/gen_golden.py --only base_full,base_noncross     # regenerate a subset
   adamw.npz      3-step HF-AdamW known-answer test computed with python floats
   state_manifest.json  key -> [shape, dtype] of the reference CXRBERT.state_dict() at BERT-base (`--only manifest`)
@@ -453,6 +459,45 @@ def main(argv=()):
         r = run_case(cx, CfgCls, b768, B=1, N=100, S=665, family="s2s", seed=24, with_grads=False, store_hidden=False, ncols=256)
         np.savez_compressed(os.path.join(OUT, "base768_s2s.npz"), **r)
         print("base768 s2s", float(r["mlm_loss"]), float(r["itm_loss"]))
+    # gradients for the mask families the cases above pin forward only (or not at all): ragged batches, so the pads fall
+    # inside the BAR / non-cross blocks and the block-sparse backward sees n2 = 38 and 12 heads at the kernels' own scale
+    for fam, seed in (("bar", 15), ("noncross", 16), ("1d", 17)):
+        if not want(f"c1_{fam}_grad"):
+            continue
+        r = run_case(cx, CfgCls, c1, B=4, N=16, S=45, family=fam, seed=seed, with_grads=True, store_hidden=False)
+        _ragged(r)
+        np.savez_compressed(os.path.join(OUT, f"c1_{fam}_grad.npz"), **r)
+        print(f"c1 {fam} grad", float(r["mlm_loss"]), float(r["itm_loss"]))
+    for name, fam, B, seed in (("base_bar", "bar", 2, 25), ("base_noncross_grad", "noncross", 2, 27),
+                               ("base_mixed_b4", "mixed", 4, 29)):
+        if not want(name):
+            continue
+        if fam == "mixed":
+            _assert_mixed_draws_both(base, B, 36, 473, seed)
+        r = run_case(cx, CfgCls, base, B=B, N=36, S=473, family=fam, seed=seed, with_grads=True, store_hidden=False)
+        _ragged(r)
+        np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **r)
+        print(name, float(r["mlm_loss"]), float(r["itm_loss"]))
+    if want("base768_s2s_grad"):
+        b768 = O.CONFIGS["base768"]
+        r = run_case(cx, CfgCls, b768, B=2, N=100, S=665, family="s2s", seed=30, with_grads=True, store_hidden=False)
+        _ragged(r)
+        np.savez_compressed(os.path.join(OUT, "base768_s2s_grad.npz"), **r)
+        print("base768 s2s grad", float(r["mlm_loss"]), float(r["itm_loss"]))
+
+
+def _ragged(r):
+    assert len(set(r["in_n_ids"].tolist())) > 1, r["in_n_ids"]
+
+
+def _assert_mixed_draws_both(cfg, B, N, S, seed):
+    """The 'mixed' case must hold both families (seed 28, for one, draws s2s for all four samples at this shape)."""
+    batch = synth.make_batch(cfg, B, N, S, "mixed", seed=seed)
+    fams = set()
+    for b in range(B):
+        m = batch["attn_mask"][b]
+        fams.add(next(f for f in ("full", "s2s") if np.array_equal(m, D.build_mask(f, N, S, int(batch["n_ids"][b])))))
+    assert fams == {"full", "s2s"}, (seed, fams)
 
 
 if __name__ == "__main__":

@@ -1110,6 +1110,98 @@ def test_attention_dropout_keep_bits_every_tile_class_and_packed_rows(dt, fam, B
     assert relerr(dq, qd.grad) < (6e-3 if dt == torch.float16 else 2.5e-2)
 
 
+# ------------------------------------------------------------------------------------------ attention at the production shapes
+# (family, B, N, S) at BERT-base geometry, 12 heads of 64: L = 512 with n2 = 38 (the image / text boundary inside the first 64-row tile)
+# and L = 768 (12 key tiles); packed rows as well for the families whose padding no valid query sees
+BASE_ATT = [("bar", 2, 36, 473), ("noncross", 2, 36, 473), ("mixed", 4, 36, 473), ("1d", 2, 36, 473), ("s2s", 2, 100, 665)]
+BASE_ATT_CASES = [(f, B, N, S, pk) for f, B, N, S in BASE_ATT for pk in ((False, True) if f in ("mixed", "1d", "s2s") else (False,))]
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("p", [0.0, 0.1])
+@pytest.mark.parametrize("fam,B,N,S,packed", BASE_ATT_CASES)
+def test_attention_at_bert_base_shapes_every_mask_family(dt, p, fam, B, N, S, packed):
+    """mv_attn_fwd / mv_attn_bwd at the shapes the model runs them, for every mask family the reference trains with, on ragged samples
+    (one with a single text token; for mixed, one without padding too), against the fp64 restatement of attn_ref (with the decoded
+    keep-bits when p > 0) on the rows that exist.  Every output holds NaN beforehand, so a block that is never written shows up; with
+    packed rows nothing may be written after a sample's packed length (lse / delta keep their [B, A, L] layout) or the last row."""
+    A, dh = 12, 64
+    H, Lq = A * dh, N + S + 3
+    g = torch.Generator().manual_seed(17)
+    n_ids = torch.randint((S + 1) // 2 + 1, S + 1, (B,), generator=g)
+    n_ids[0] = 2                                            # one text token and its [SEP]
+    if B > 2:
+        n_ids[1] = S + 1                                    # no padding
+    if fam == "mixed":
+        fams, mask = ["s2s" if i % 2 == 0 else "full" for i in range(B)], D.mixed_mask(N, S, n_ids, torch.arange(B) % 2 == 0)
+    else:
+        fams, mask = fam, D.build_mask(fam, N, S, n_ids)
+    desc = D.MaskDesc.make(fams, N, S, n_ids, DEV)
+    assert desc.packable() == (fam in ("mixed", "1d", "s2s"))
+    mask = mask.to(DEV)
+    bits = torch.zeros((B, Lq, (Lq + 31) // 32), dtype=torch.int32, device=DEV)
+    tinfo = torch.zeros((B, (Lq + 63) // 64, (Lq + 63) // 64), dtype=torch.uint8, device=DEV)
+    ops.mask_build(desc.desc, B, Lq, bits, tinfo)           # the model runs on the descriptors' bits ...
+    bits2, tinfo2 = torch.zeros_like(bits), torch.zeros_like(tinfo)
+    ops.mask_pack(mask, bits2, tinfo2)
+    assert torch.equal(bits, bits2)                          # ... which say what the dense mask says
+    cu, M, lens = None, B * Lq, [Lq] * B
+    if packed:
+        cu, _, _ = ops.pack_plan(desc.desc, B, Lq)
+        M = int(cu[-1])
+        lens = (cu[1:] - cu[:-1]).tolist()
+        assert lens == (N + 2 + n_ids).tolist()
+    db, keep = None, None
+    if p > 0:
+        db = torch.zeros((ops.dropbits_numel(B, Lq, A),), dtype=torch.int32, device=DEV)
+        ops.attn_dropmask(p, 0x5EED5, B, Lq, A, db, cu=cu)
+        keep = ops.attn_keep_mask(db, B, Lq, A).double() * (65536.0 / (65536.0 - 6554.0))
+    G = 64                                                   # guard rows after the last one the kernels may write
+    qkv, dctx = rnd((M, 3 * H), dt, 61), rnd((M, H), dt, 62)
+    ctx_buf = torch.full((M + G, H), float("nan"), dtype=dt, device=DEV)
+    dq_buf = torch.full((M + G, 3 * H), float("nan"), dtype=dt, device=DEV)
+    lse = torch.full((B, A, Lq), float("nan"), dtype=torch.float32, device=DEV)
+    delta = torch.full((B, A, Lq), float("nan"), dtype=torch.float32, device=DEV)
+    ctx, dq = ctx_buf[:M], dq_buf[:M]
+    kw = dict(p_drop=p, cu=cu, total_rows=M if packed else 0, dropbits=db)
+    ops.attn_fwd(qkv, bits, tinfo, ctx, lse, B, Lq, A, dh, **kw)
+    ops.attn_bwd(qkv, ctx, dctx, lse, bits, tinfo, dq, delta, B, Lq, A, dh, **kw)
+    # fp64 restatement sample by sample on the rows that exist
+    qd = qkv.double().requires_grad_(True)
+    m3 = mask if mask.dim() == 3 else mask[:, None, :].expand(B, Lq, Lq)
+    outs, lses, row0 = [], [], 0
+    for b in range(B):
+        n = lens[b]
+        q, k, v = [t.view(n, A, dh).permute(1, 0, 2) for t in qd[row0:row0 + n].split(H, dim=-1)]
+        s = q @ k.transpose(-1, -2) / math.sqrt(dh) + ((1.0 - m3[b, :n, :n].double()) * -10000.0)[None]
+        pr = torch.softmax(s, -1)
+        if keep is not None:
+            pr = pr * keep[b, :, :n, :n]
+        outs.append((pr @ v).permute(1, 0, 2).reshape(n, H))
+        lses.append(torch.logsumexp(s.detach(), -1))
+        row0 += n
+    rctx = torch.cat(outs)
+    # tolerances of test_attention_fwd_bwd (p = 0) and test_attention_dropout_keep_bits_every_tile_class_and_packed_rows (p > 0)
+    f16 = dt == torch.float16
+    tf, tb = ((3e-3, 4e-3) if f16 else (1.5e-2, 2e-2)) if p == 0 else ((4e-3, 6e-3) if f16 else (2e-2, 2.5e-2))
+    assert bool(torch.isfinite(ctx.float()).all())
+    e_ctx = relerr(ctx, rctx)
+    rdelta = (dctx.double() * ctx.double()).view(M, A, dh).sum(-1)          # sum_d dctx * ctx of the kernel's own (rounded) context
+    row0 = 0
+    for b in range(B):
+        n = lens[b]
+        assert float((lse[b, :, :n].double() - lses[b]).abs().max()) < 2e-2, b
+        assert relerr(delta[b, :, :n], rdelta[row0:row0 + n].t()) < 1e-4, b
+        assert bool(torch.isnan(lse[b, :, n:]).all()) and bool(torch.isnan(delta[b, :, n:]).all()), b
+        row0 += n
+    (rctx * dctx.double()).sum().backward()
+    assert bool(torch.isfinite(dq.float()).all())
+    e_dq = relerr(dq, qd.grad)
+    print(f"{fam} B={B} L={Lq} packed={packed} p={p} {dt}: ctx {e_ctx:.2e} (< {tf}), dqkv {e_dq:.2e} (< {tb})")
+    assert e_ctx < tf and e_dq < tb
+    assert bool(torch.isnan(ctx_buf[M:].float()).all()) and bool(torch.isnan(dq_buf[M:].float()).all())
+
+
 # ------------------------------------------------------------------------------------------ last layer: consumed rows first, query limits
 def test_tail_perm_orders_the_consumed_rows_first():
     g = torch.Generator().manual_seed(3)

@@ -78,10 +78,12 @@ def test_forward_matches_reference_golden(golden_dir, name, dtype, tol):
     assert abs(float(ml) - float(z["mlm_loss"])) < tol and abs(float(il) - float(z["itm_loss"])) < tol
 
 
-@pytest.mark.parametrize("name", ["c1_full", "c1_s2s", "c1v1k_full", "c1v1k_bar_ragged", "c1v1k_nopos"])
+@pytest.mark.parametrize("name", ["c1_full", "c1_s2s", "c1v1k_full", "c1v1k_bar_ragged", "c1v1k_nopos", "c1_bar_grad", "c1_noncross_grad",
+                                  "c1_1d_grad", "base_bar"])
 @pytest.mark.parametrize("dtype,rtol", [(torch.float32, 1e-3), (torch.bfloat16, 4e-2)])
 def test_dropin_backward_matches_reference_gradients(golden_dir, name, dtype, rtol):
-    """loss.backward() through CXRBERT.forward, exactly as train_origin.py:106-130 does."""
+    """loss.backward() through CXRBERT.forward, exactly as train_origin.py:106-130 does -- on every mask family, and once at BERT-base
+    under BAR, the mask of the unchanged main_origin.py loop."""
     z, meta, cfg, P, b = load_case(golden_dir, name)
     model = make_model(cfg, P, dtype)
     mlm, itm = fwd(model, b)
@@ -521,32 +523,69 @@ def test_pure_bf16_forward_operands_stay_within_their_measured_bound(golden_dir)
     assert d.mean() < 6e-3 and d.max() < 3.5e-2
 
 
-@pytest.mark.parametrize("case", ["base_full", "base_full_b4"])
+def _reference_mask_families(b, N, S):
+    """Per-sample family of the reference's dense masks, by comparison with each closed form (not by the recogniser under test)."""
+    out = []
+    for i in range(b["attn_mask"].shape[0]):
+        n = b["n_ids"][i:i + 1]
+        out.append(next(f for f in mv.data.FAMILIES if torch.equal(mv.data.build_mask(f, N, S, n)[0], b["attn_mask"][i])))
+    return out
+
+
+def _trainer_descriptors(b, N):
+    """MaskDesc of the reference's dense masks as the drop-in trainer derives them (CXRBERT_Trainer._recognise_masks: probe rows) and
+    checks them (mv_mask_verify_host: every entry) before a step runs on them."""
+    from medvill_amd.trainer import CXRBERT_Trainer
+    tr = object.__new__(CXRBERT_Trainer)
+    tr.args = SimpleNamespace()
+    tr._init_mask_policy(tr.args)
+    desc = tr._recognise_masks(b["attn_mask"], b["input_txt"], N, b["txt_labels"])
+    assert desc is not None
+    assert mv.hip_ops.mask_verify_host(b["attn_mask"], desc.host_desc()) == -1
+    return desc
+
+
+# BERT-base with the reference's gradients: config 2's family (B = 2 / 4), BAR (the reference's default mask), non-cross (config 4), per-
+# sample full / s2s (config 3's batch form) and L = 768 seq2seq (config 5); every batch ragged
+BASE_GRAD_CASES = ["base_full", "base_full_b4", "base_bar", "base_noncross_grad", "base_mixed_b4", "base768_s2s_grad"]
+
+
+@pytest.mark.parametrize("case", BASE_GRAD_CASES)
 @pytest.mark.parametrize("dtype,rtol,pack", [(torch.float32, 1e-3, False), (torch.bfloat16, 4e-2, False), (torch.bfloat16, 4e-2, True)])
 def test_bert_base_gradients_against_reference_golden(golden_dir, dtype, rtol, pack, case):
-    """Config 2's family at scale (BERT-base, 12 layers, L=512, bidirectional, B=2 / B=4 ragged): the fused training step's gradient
-    of EVERY parameter against the reference's loss.backward() (norm + 16 sampled entries per tensor).  pack=True is the path
-    bench.py times and CXRBERT_Trainer runs -- TrainStep's defaults: mask descriptors, padding removed (packed rows), the last layer on
-    the consumed rows only with those rows as its only queries (`tq`), the MLM head on the labelled rows only, f16 operands and loss-
-    scaled f16 gradients -- held to the same tolerances as the padded path."""
+    """BERT-base at scale (12 layers, 12 heads, L = 512 / 768, ragged batches): the fused training step's gradient of EVERY parameter
+    against the reference's loss.backward() (norm + 16 sampled entries per tensor).  pack=False runs on the reference's dense masks,
+    every row.  pack=True is the path bench.py times and CXRBERT_Trainer runs -- TrainStep's defaults on the descriptors the trainer
+    derives from those dense masks: padding removed (packed rows) where the family allows it (full, s2s, mixed), padded rows for BAR and
+    non-cross (a valid query sees the pads there), the last layer on the consumed rows only -- with those rows as its only queries
+    (`tq`) when every sample is bidirectional --, the MLM head on the labelled rows only, f16 operands and loss-scaled f16 gradients;
+    held to the same tolerances as the padded path."""
     z, meta, cfg, P, b = load_case(golden_dir, case)
+    N, S, B = meta["N"], meta["S"], meta["B"]
+    fams = _reference_mask_families(b, N, S)
+    assert set(fams) == ({"full", "s2s"} if meta["family"] == "mixed" else {meta["family"]})
     model = make_model(cfg, P, dtype)
     batch = dict(b)
+    packed = False
     if pack:
-        batch["attn_desc"] = mv.data.MaskDesc.make("full", meta["N"], meta["S"], b["n_ids"], DEV)
+        desc = _trainer_descriptors(b, N)
+        assert torch.equal(desc.host_desc(), mv.data.MaskDesc.make(fams, N, S, b["n_ids"]).host_desc())      # the recognised families
+        packed = desc.packable()
+        assert packed == (meta["family"] in ("full", "s2s", "mixed"))
+        batch["attn_desc"] = desc.to(DEV)
         ts = mv.TrainStep(model, lr=0.0)                                      # the defaults ARE the benchmarked path
         assert ts.pack_rows and ts.tail_rows and model.engine.tail_queries
     else:
         ts = mv.TrainStep(model, lr=0.0, pack_rows=False)
     stats = ts(batch, train=True).cpu()
     eng = model.engine
+    assert (eng.S["cu"] is not None) == packed                                # which layout really ran
+    assert (eng.S["tq"] is not None) == (packed and set(fams) == {"full"})
     if pack:
-        Lq = meta["N"] + meta["S"] + 3
-        assert eng.S["cu"] is not None and eng.S["tq"] is not None and eng.S["sel"] is not None and eng.S["M"] < meta["B"] * Lq
+        Lq = N + S + 3
+        assert eng.S["sel"] is not None and (eng.S["M"] < B * Lq) == packed
         assert eng.dt == mv._lib.MV_F16 and eng.fdt == mv._lib.MV_F16
         assert float(eng.scaler[6]) == 0.0                                    # no non-finite gradient under the loss scale
-    else:
-        assert eng.S["cu"] is None
     tol = FP32_TOL if dtype == torch.float32 else BF16_TOL
     if "lab_rows" in z.files:
         # the labelled-rows-only MLM head against the reference's logits AT those rows, entry by entry (1,024 sampled columns of
@@ -578,10 +617,12 @@ def test_bert_base_gradients_against_reference_golden(golden_dir, dtype, rtol, p
         worst = max(worst, e1, e2 * 0.25)
         table.append((e2, e1, k, ref_norm))
     table.sort(reverse=True)
-    print(f"{case} {dtype} pack={pack}: worst gradient deviation {worst:.2e}; largest entry deviations: "
+    print(f"{case} ({meta['family']}, {'packed' if packed else 'padded'} rows) {dtype} pack={pack}: worst gradient deviation {worst:.2e}; "
+          f"loss |d| mlm {abs(float(stats[0] / stats[1]) - float(z['mlm_loss'])):.1e} itm {abs(float(stats[3] / stats[4]) - float(z['itm_loss'])):.1e}; "
+          "largest entry deviations: "
           + "; ".join(f"{k} e2={e2:.3f} e1={e1:.4f} |g|={n:.2e}" for e2, e1, k, n in table[:6]))
     # norm of every tensor within rtol; single entries within 4 rtol of the tensor's scale -- 6 rtol for the two head weights whose
-    # gradient is a sum of B = 2 outer products (pooler, ITM): their entries are heavy-tailed (a few are tens of RMS), so one
+    # gradient is a sum of B = 2 / 4 outer products (pooler, ITM): their entries are heavy-tailed (a few are tens of RMS), so one
     # operand's bf16 rounding (2^-9 of such an entry) is a visible fraction of the RMS the error is scaled by (norm error 1.2 %)
     for e2, e1, k, n in table:
         assert e1 < rtol, (k, e1, n)
