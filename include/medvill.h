@@ -483,6 +483,41 @@ int mv_bce_fwd_bwd(const float* logits, int ld, const float* target, const int32
 int mv_rows_mul(int dtype, const void* a, int lda, const int32_t* rows_a, const void* b, int ldb, const int32_t* rows_b, int R, int H,
                 void* out, int ldo, void* stream);
 
+/* ---- BertAdam and multi-label classification (csrc/mv_optim.hip) ------------------------------------
+ * The optimizer of every fine-tuning program of the reference (pytorch_pretrained_bert/optimization.py:57-182).  Additive entry points.
+ *
+ * Both optimizer calls read two device tables over a flat f32 buffer of n elements (n % 4 == 0, 16-byte aligned):
+ *   tensors int64 [T, 4] = {offset, count, first_chunk, flags}; offset % 64 == 0; flags bit 0: weight decay applies, bit 1: active
+ *   chunks  int32 [NC]   = tensor id per chunk of MV_OPTIM_CHUNK elements; tensor t owns chunks first_chunk ..
+ *                          first_chunk + ceil(count / MV_OPTIM_CHUNK) - 1, in element order
+ * mv_tensor_sqnorms: out[t] = sum of x[offset .. offset + count)^2 for every active tensor (0 for an inactive one); partials is an
+ *   f32 [NC] workspace.  Fixed summation order, no atomics: the same input gives the same bits on every run.
+ * mv_bertadam_step: for every element of every active tensor
+ *     g' = g * min(1, max_grad_norm / (sqrt(sqnorms[t]) + 1e-6))        (max_grad_norm > 0; sqnorms from mv_tensor_sqnorms)
+ *     m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2  (1 - b formed in double, rounded once);  u = m / (sqrt(v) + eps) [+ weight_decay * p when flagged]
+ *     p -= lr_t u,  lr_t = lr * schedule(step / t_total, warmup) (t_total == -1: lr), no bias correction; `step` is the number of
+ *     updates applied BEFORE this one.  shadow_bf16 / shadow_f16 (nullable) receive the updated p.  g is not modified.  Elements
+ *     outside every tensor and inactive tensors are neither read nor written.
+ *   scaler_state (nullable, as mv_adamw_step): state[3] != 0 skips the whole step; otherwise step = max(state[4] - 1, 0) (mv_scaler_update
+ *     has already counted the step being applied), so a skipped step does not advance the schedule.
+ * mv_bce_multilabel (the loss of the diagnosis classifier, Downstream_task/Classification/mmbt/main.py:93-101): per row of logits
+ *   [R, ld] (f32), multi-hot targets [R, C] (f32, contiguous) and pos_weight w [C] (nullable = 1):
+ *     *loss += sum_c (1 - y) z + (1 + (w - 1) y) (max(-z, 0) + log1p(exp(-|z|)))                  (the SUM; mean = / (R*C))
+ *     dgrad[r, c] = (sigmoid(z) (w y + 1 - y) - w y) * g * S for c < C, 0 for C <= c < ldd         (g, S as mv_bce_fwd_bwd)
+ *     probs[r, c] = sigmoid(z)  (f32 [R, C]);  counters f32 [3, C] += {tp, fp, fn} with prediction z > 0 and label y > 0.5
+ *   target, pos_weight, loss, dgrad, probs and counters are each nullable (loss, dgrad and counters need target).                */
+#define MV_OPTIM_CHUNK 4096
+enum { MV_SCHED_WARMUP_LINEAR = 0, MV_SCHED_WARMUP_CONSTANT = 1, MV_SCHED_WARMUP_COSINE = 2 };
+int mv_tensor_sqnorms(const float* x, size_t n, const int64_t* tensors, int T, const int32_t* chunks, int NC, float* partials,
+                      float* out, void* stream);
+int mv_bertadam_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, void* shadow_f16, size_t n,
+                     const int64_t* tensors, int T, const int32_t* chunks, int NC, const float* sqnorms, double lr, double b1, double b2,
+                     float eps, float weight_decay, float max_grad_norm, int step, int t_total, double warmup, int schedule,
+                     const float* scaler_state, void* stream);
+int mv_bce_multilabel(const float* logits, int ld, const float* target, const float* pos_weight, int R, int C, float* loss,
+                      void* dgrad, int d_dtype, int ldd, const float* grad_scale_dev, float grad_scale_host,
+                      const float* loss_scale_dev, float* probs, float* counters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_DGELU, EPI_RES, EPI_BIAS_TA
 _ERR = {-1: "MV_E_ARG (null pointer / bad size)", -2: "MV_E_SHAPE (unsupported shape or alignment)",
         -3: "MV_E_DTYPE", -4: "MV_E_WORKSPACE (workspace too small)", -5: "MV_E_NO_RCCL (librccl could not be loaded)"}
 
-vp, i32, i64, f32, sz, u64 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_ulonglong
+vp, i32, i64, f32, sz, u64, f64 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_ulonglong, C.c_double
 
 # name -> argtypes; every function returns int unless listed in _RESTYPE.  This table is also
 # what tests/test_abi.py checks against include/medvill.h.
@@ -83,6 +83,10 @@ PROTOTYPES = {
     # VQA (csrc/mv_vqa.hip)
     "mv_bce_fwd_bwd": [vp, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, f32, vp, vp, vp, vp],
     "mv_rows_mul": [i32, vp, i32, vp, vp, i32, vp, i32, i32, vp, i32, vp],
+    # BertAdam (csrc/mv_optim.hip)
+    "mv_tensor_sqnorms": [vp, sz, vp, i32, vp, i32, vp, vp, vp],
+    "mv_bce_multilabel": [vp, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, f32, vp, vp, vp, vp],
+    "mv_bertadam_step": [vp, vp, vp, vp, vp, vp, sz, vp, i32, vp, i32, vp, f64, f64, f64, f32, f32, f32, i32, i32, f64, i32, vp, vp],
 }
 # include/medvill_debug.h: exported by libmedvill_hip_dbg.so only
 DEBUG_PROTOTYPES = {"mv_debug_set_knob": [i32, i32], "mv_debug_get_knob": [i32]}

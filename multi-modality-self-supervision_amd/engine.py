@@ -760,6 +760,15 @@ class Engine:
         self._dW(ditm8, S["pooled"], g["itm.linear.weight"], 2, H, B, lda=8, ldb=H)
         dpool = self._buf("dpool", (B, H), self.adt)
         ops.gemm(ditm8, self.w["itm.linear.weight"], dpool, tb=True, M=B, N=H, K=2, lda=8, ldb=H)
+        self._pooler_backward(dpool)
+
+    def _pooler_backward(self, dpool):
+        """dpool [B,H] compute dtype = gradient of the pooled vector tanh(Wp . h[CLS] + bp): tanh backward, the pooler's parameter
+        gradients, and dh[CLS] added into dhidden (rows b*L; packed rows cu[b]; the B first rows of a compact final state).  Shared
+        by the ITM head and the diagnosis classifier (classification.py)."""
+        S, H = self.S, self.cfg.hidden
+        B, Lq = S["B"], S["L"]
+        g, us = self.g, self.unscale_dev
         dpre = self._buf("dpoolpre", (B, H), self.adt)
         ops.dact(1, dpool, S["pooled"], dpre, B * H)
         ops.colsum(dpre, H, B, H, g["enc.pooler.dense.bias"], accumulate=True, unscale=us)

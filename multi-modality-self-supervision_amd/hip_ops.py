@@ -593,3 +593,61 @@ def rows_mul(a, rows_a, b, rows_b, out, *, R, H, lda=None, ldb=None, ldo=None):
                             L.ptr(rows_b), R, H, L.ptr(out), ldo if ldo is not None else H, L.stream_ptr())
     L.check(rc, f"mv_rows_mul(R={R},H={H})")
     return out
+
+
+# ---- BertAdam (csrc/mv_optim.hip) ----
+OPTIM_CHUNK = 4096                       # MV_OPTIM_CHUNK of include/medvill.h
+SCHEDULE_IDS = {"warmup_linear": 0, "warmup_constant": 1, "warmup_cosine": 2}
+
+
+def tensor_sqnorms(x, tensors, chunks, partials, out):
+    """out[t] = sum of squares of tensor t of the flat f32 buffer x (tables: see mv_tensor_sqnorms; bit-reproducible)."""
+    L.require_cuda(x, tensors, chunks, partials, out)
+    if x.dtype != torch.float32 or tensors.dtype != torch.int64 or chunks.dtype != torch.int32 or partials.dtype != torch.float32 \
+            or out.dtype != torch.float32:
+        raise TypeError("tensor_sqnorms: f32 data, int64 tensor table, int32 chunk table")
+    T, NC = int(tensors.shape[0]), int(chunks.numel())
+    if tensors.dim() != 2 or tensors.shape[1] != 4 or not tensors.is_contiguous() or partials.numel() < NC or out.numel() < T:
+        raise ValueError("tensor_sqnorms: tensors [T, 4] contiguous, partials [NC], out [T]")
+    rc = _lib().mv_tensor_sqnorms(L.ptr(x), x.numel(), L.ptr(tensors), T, L.ptr(chunks), NC, L.ptr(partials), L.ptr(out), L.stream_ptr())
+    L.check(rc, "mv_tensor_sqnorms")
+    return out
+
+
+def bertadam_step(p, g, m, v, tensors, chunks, sqnorms, *, lr, step, warmup=-1.0, t_total=-1, schedule="warmup_linear", b1=0.9, b2=0.999,
+                  eps=1e-6, weight_decay=0.01, max_grad_norm=1.0, shadow=None, shadow_f16=None, scaler_state=None):
+    """One BertAdam update of every active tensor of the flat buffers (see mv_bertadam_step); `step` = updates applied before this one."""
+    L.require_cuda(p, g, m, v, tensors, chunks, sqnorms, shadow, shadow_f16, scaler_state)
+    if any(t.dtype != torch.float32 for t in (p, g, m, v)) or tensors.dtype != torch.int64 or chunks.dtype != torch.int32:
+        raise TypeError("bertadam_step: f32 buffers, int64 tensor table, int32 chunk table")
+    n = p.numel()
+    if any(t.numel() != n for t in (g, m, v)) or any(t is not None and t.numel() != n for t in (shadow, shadow_f16)):
+        raise ValueError("bertadam_step: p, g, m, v and the 16-bit copies have one size")
+    T, NC = int(tensors.shape[0]), int(chunks.numel())
+    if tensors.dim() != 2 or tensors.shape[1] != 4 or not tensors.is_contiguous() or (sqnorms is not None and sqnorms.numel() < T):
+        raise ValueError("bertadam_step: tensors [T, 4] contiguous, sqnorms [T]")
+    rc = _lib().mv_bertadam_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(shadow), L.ptr(shadow_f16), n, L.ptr(tensors), T,
+                                 L.ptr(chunks), NC, L.ptr(sqnorms), float(lr), float(b1), float(b2), float(eps), float(weight_decay),
+                                 float(max_grad_norm), int(step), int(t_total), float(warmup), SCHEDULE_IDS[schedule],
+                                 L.ptr(scaler_state), L.stream_ptr())
+    L.check(rc, "mv_bertadam_step")
+
+
+def bce_multilabel(logits, C, *, R=None, ld=None, target=None, pos_weight=None, loss=None, dgrad=None, ldd=None, grad_scale=1.0,
+                   grad_scale_dev=None, loss_scale_dev=None, probs=None, counters=None):
+    """BCEWithLogitsLoss(pos_weight) over multi-hot targets [R, C]: loss SUM added to loss[0], gradient (padding columns C..ldd zero),
+    sigmoid probabilities [R, C] and the f32 [3, C] {tp, fp, fn} counters (see mv_bce_multilabel).  Every output is optional."""
+    L.require_cuda(logits, target, pos_weight, loss, dgrad, grad_scale_dev, loss_scale_dev, probs, counters)
+    if logits.dtype != torch.float32 or any(t is not None and (t.dtype != torch.float32 or not t.is_contiguous())
+                                            for t in (target, pos_weight, loss, probs, counters)):
+        raise TypeError("bce_multilabel: f32 logits; contiguous f32 targets, pos_weight, loss, probs and counters")
+    R = R if R is not None else logits.shape[0]
+    if (target is not None and target.numel() != R * C) or (pos_weight is not None and pos_weight.numel() != C) \
+            or (probs is not None and probs.numel() != R * C) or (counters is not None and counters.numel() != 3 * C):
+        raise ValueError("bce_multilabel: target / probs [R, C], pos_weight [C], counters [3, C]")
+    ld = ld if ld is not None else logits.stride(0)
+    ldd = ldd if ldd is not None else (dgrad.stride(0) if dgrad is not None else 0)
+    rc = _lib().mv_bce_multilabel(L.ptr(logits), ld, L.ptr(target), L.ptr(pos_weight), R, C, L.ptr(loss), L.ptr(dgrad),
+                                  L.dt_of(dgrad) if dgrad is not None else 0, ldd, L.ptr(grad_scale_dev), float(grad_scale),
+                                  L.ptr(loss_scale_dev), L.ptr(probs), L.ptr(counters), L.stream_ptr())
+    L.check(rc, f"mv_bce_multilabel(R={R},C={C})")

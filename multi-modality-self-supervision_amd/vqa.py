@@ -11,7 +11,7 @@ The answer classifier is Linear(H, 2H) + ReLU + Linear(2H, A) (model.py:939-943)
 its last layer's per-row work on the rows the classifier reads only (Engine.encoder_forward, tail_rows); the classifier's products,
 BCEWithLogits, its gradient and the score split are HIP kernels (mv_gemm_rows / mv_gemm, mv_bce_fwd_bwd, mv_dact mode 2, mv_rows_mul).
 The classifier's parameters live in a small flat buffer of their own (fp32 master + the 16-bit copies the kernels read), which
-medvill_amd.optim.AdamW updates with one more fused launch.  Arithmetic is CXRBERT's (the pretrained model), DESIGN.md "8b. VQA".
+medvill_amd.optim.AdamW / BertAdam update with one more fused launch.  Arithmetic is CXRBERT's (the pretrained model), DESIGN.md "8b. VQA".
 """
 from __future__ import annotations
 
@@ -113,6 +113,12 @@ class CXRBertForVQA(nn.Module):
     .bert is the CXRBERT; .ans_classifier the Sequential(Linear, ReLU, Linear) whose Parameters are views of the classifier's flat buffer.
     `attn_mask` may be a materialised mask or data.MaskDesc descriptors (16-bit: the encoder then runs on the valid rows only)."""
 
+    # medvill_amd.optim.BertAdam: the classifier's tensors, and the encoder tensors the VQA graph never reaches (`grad is None` in the
+    # reference: no update, no weight decay)
+    _head_keys = HEAD_KEYS
+    _padded_key = HEAD_KEYS[2]            # the weight whose rows are padded to Ap inside the flat buffer
+    _unreached = ("mlm.", "itm.", "enc.pooler.")
+
     def __init__(self, config, args=None, n_answers=N_ANSWERS, **kw):
         super().__init__()
         self.bert = CXRBERT(config, args, **kw)
@@ -131,7 +137,7 @@ class CXRBertForVQA(nn.Module):
         self.head_shf = torch.zeros(self._n_head, dtype=torch.float16, device=dev) if eng.shadow_f is not None else None
         self.ans_classifier = nn.Sequential(nn.Linear(H, 2 * H), nn.ReLU(), nn.Linear(2 * H, A))
         self._hplist = []
-        for name in HEAD_KEYS:
+        for name in self._head_keys:
             idx, leaf = name.split(".")[1:]
             par = nn.Parameter(self._view(self.head_p, name), requires_grad=True)
             par._medvill_head = weakref.ref(self)          # medvill_amd.optim.AdamW finds the classifier's flat buffers through it
@@ -145,7 +151,7 @@ class CXRBertForVQA(nn.Module):
     # ------------------------------------------------------------------ classifier storage
     def _view(self, buf, name, padded=False):
         off, shape = self._layout[name]
-        if padded and name == HEAD_KEYS[2]:
+        if padded and name == self._padded_key:
             shape = (self.Ap, shape[1])
         n = 1
         for s in shape:
@@ -156,10 +162,10 @@ class CXRBertForVQA(nn.Module):
         return self.head_p if dt == MV_F32 else (self.head_shf if dt == MV_F16 else self.head_sh)
 
     def _rebind(self):
-        for name, par in zip(HEAD_KEYS, self._hplist):
+        for name, par in zip(self._head_keys, self._hplist):
             par.data = self._view(self.head_p, name)
         if self.head_g is not None:
-            for name, par in zip(HEAD_KEYS, self._hplist):
+            for name, par in zip(self._head_keys, self._hplist):
                 if par.grad is not None and par.grad.device != self.head_g.device:
                     par.grad = None
 
@@ -187,13 +193,13 @@ class CXRBertForVQA(nn.Module):
         self._head_versions = sum(p._version for p in self._hplist)
 
     def _head_holds_views(self):
-        return any(p.grad is not None and p.grad.data_ptr() == self._view(self.head_g, n).data_ptr() for n, p in zip(HEAD_KEYS, self._hplist))
+        return any(p.grad is not None and p.grad.data_ptr() == self._view(self.head_g, n).data_ptr() for n, p in zip(self._head_keys, self._hplist))
 
     def _hand_over_head(self, views):
         """The classifier's gradients -> torch, by the rule of cxrbert._hand_over_grads (views of the flat gradient unless a hook or a
         process group asks for copies)."""
         out = []
-        for name, p in zip(HEAD_KEYS, self._hplist):
+        for name, p in zip(self._head_keys, self._hplist):
             g = self._view(self.head_g, name)
             if views and (p.grad is None or p.grad.data_ptr() == g.data_ptr()):
                 p.grad = g
@@ -370,7 +376,7 @@ class CXRBertForVQA(nn.Module):
             raise RuntimeError("some classifier Parameters have a gradient and some have none: the flat update cannot skip individual tensors")
         if self.head_g is None:
             self.head_g = torch.zeros_like(self.head_p)
-        for name, g in zip(HEAD_KEYS, grads):
+        for name, g in zip(self._head_keys, grads):
             gv = self._view(self.head_g, name)
             if g.data_ptr() != gv.data_ptr():
                 gv.copy_(g)
