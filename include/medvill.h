@@ -315,7 +315,9 @@ int mv_embed_bwd(int dtype, const void* dx0, const float* pre, const float* mean
  * Replaces nn.CrossEntropyLoss(ignore_index=-100) on mlm.transpose(1,2) and
  * nn.CrossEntropyLoss() on the ITM logits (train_origin.py:62-63,120-126) plus the argmax
  * metrics of train_origin.py:133-146, fused with the loss gradient.
- * logits [R, ld] (l_dtype f32 or bf16); labels int32 [R] (-100 = ignored row);
+ * logits [R, ld] (l_dtype f32, bf16 or f16); labels int32 [R] (-100 = ignored row);
+ * any label outside 0..V-1 (negative, or >= V where torch would raise) is an ignored row: no loss,
+ * no count, a zero gradient row; the logits of such a row are not read.
  * out[0] += sum of nll over labelled rows, out[1] += #labelled rows, out[2] += #rows whose
  * argmax == label (f32 accumulators, zero them first).
  * dlogits (nullable; d_dtype) = (softmax - onehot) * grad_scale for labelled rows, 0 otherwise;
@@ -329,7 +331,9 @@ int mv_ce_fwd_bwd(const void* logits, int l_dtype, int ld, const int32_t* labels
 
 /* ---- row gather / scatter (labelled-row compaction for the MLM head) ------------------------
  * dst[i,:] = src[rows[i],:]  /  dst[rows[i],:] (+)= src[i,:]; rows int32 [R].  A negative rows[i] means "no such
- * row" (a position dropped by mv_pack_plan): gather writes zeros, scatter writes nothing.          */
+ * row" (a position dropped by mv_pack_plan): gather writes zeros, scatter writes nothing.
+ * scatter: the non-negative rows[i] must be distinct -- two source rows with the same destination race (with or without
+ * accumulate) and the result is unspecified.  accumulate adds in f32 and rounds once to dtype.          */
 int mv_gather_rows(int dtype, const void* src, int lds, const int32_t* rows, int R, int H,
                    void* dst, int ldd, void* stream);
 int mv_scatter_rows(int dtype, const void* src, int lds, const int32_t* rows, int R, int H,
