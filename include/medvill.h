@@ -446,14 +446,15 @@ int mv_scaler_update(float* state, int growth_interval, float growth, float back
  *     ctx[r, h] = sum_j softmax_j( q[r,h] . K[s_j, h] / sqrt(dh) ) V[s_j, h],   s_j = slots[row(r)][j], j < nk[r]
  *   row(r) = slot_row[r] (int32, nullable: r) -- beams of one sample share a table row prefix, and the MASK row and the token row
  *   of one beam share one table row with different nk.  K / V caches: [slots, ldkv] in dtype (f32, bf16, f16), f32 softmax.
- *   max_nk >= every nk[r] (host bound; picks the split count).  dh <= 128, 256 % dh == 0.
+ *   max_nk >= every nk[r] (host bound; picks the split count).  dh <= 128, 256 % dh == 0.  nk[r] = 0 yields a zero context row.
  *   nsplit: 1 = one pass; > 1 = split-KV: the key list is cut in nsplit ranges whose (context, max, sum) partials go to ws
  *   (>= nsplit * R * A * (dh + 2) floats) and are merged through the log-sum-exp; 0 = the library picks (as many as ws holds).
  * mv_logprob_topk: per row of logits [R, ld] (f32): lse = log sum exp, logp = x - lse; eos_penalty_id >= 0 sets logp of that
  *   column to -10000.0 (after the normalisation, as the reference's min_len rule); vals f32 [R,k] / idx int64 [R,k] = the k
  *   largest logp (k <= 16) in descending order, ties to the lower column.  lse (nullable) f32 [R].  No [R,V] output.
+ *   A -inf logit adds nothing to lse and ranks last (logp -inf, by column); a row that is -inf throughout is outside the contract.
  * mv_embed_rows: out[r] = LN(E[ids[r]] + Ty[seg[r]] + P[pos[r]]) (HF BertEmbeddings of one token), tables in dtype, gamma /
- *   beta f32; indices int64, clamped into their tables.                                                                      */
+ *   beta f32; indices int64, clamped into their tables.  The tables are dense: row i of E / P / Ty starts at element i * H.  */
 int mv_gemm_rows(int dtype, int M, int N, int K, const void* x, int ldx, const void* W, int ldw, void* C, int ldc, int c_dtype,
                  const float* bias, int epi, const void* R, int ldr, int r_dtype, void* stream);
 int mv_attn_decode(int dtype, const void* q, int ldq, const void* k_cache, const void* v_cache, int ldkv, const int32_t* slots,

@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void logprob_topk_kernel(const float* __restri
   for (int c = tid; c < V; c += 256) {
     const float xv = x[c];
     if (xv > m) { s = s * __expf(m - xv) + 1.f; m = xv; }
-    else s += __expf(xv - m);
+    else if (xv > -INFINITY) s += __expf(xv - m);       // a -inf logit adds nothing (with m still -inf, xv - m would be NaN)
     if (c != eos) tk_insert<KM>(v, ix, xv, c);
   }
   // log-sum-exp of the row

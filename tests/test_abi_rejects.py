@@ -91,6 +91,43 @@ def test_rowop_rejects(lib):
     assert lib.mv_count_nonfinite(None, 16, P, None) == E_ARG
 
 
+def test_decode_rejects(lib):
+    """mv_decode.hip: one assertion per documented condition; every call returns before a launch."""
+    gr = lambda **k: lib.mv_gemm_rows(k.get("dt", BF16), k.get("M", 16), k.get("N", 64), k.get("K", 64), k.get("x", P), k.get("ldx", 64), k.get("W", P),
+                                      k.get("ldw", 64), k.get("c", P), k.get("ldc", 64), k.get("cdt", F32), k.get("bias", P), k.get("epi", 0),
+                                      k.get("r", P), k.get("ldr", 64), k.get("rdt", BF16), None)
+    assert gr(x=None) == E_ARG and gr(W=None) == E_ARG and gr(c=None) == E_ARG and gr(M=0) == E_ARG
+    assert gr(dt=F32) == E_DTYPE and gr(cdt=3) == E_DTYPE                                   # 16-bit operands only
+    assert gr(M=257) == E_SHAPE                                                             # M <= 256
+    assert gr(K=48, ldx=48, ldw=48) == E_SHAPE                                              # K % 32
+    assert gr(ldx=68) == E_SHAPE and gr(ldw=68) == E_SHAPE                                  # leading dimensions: multiples of 8
+    assert gr(ldx=56) == E_SHAPE and gr(ldw=56) == E_SHAPE and gr(ldc=63) == E_SHAPE        # ... and not below K / N
+    assert gr(x=P + 8) == E_SHAPE and gr(W=P + 8) == E_SHAPE                                # 16-byte alignment of x and W
+    for epi in (4, 5, 6, 7, 8, 10, 11, -1):                                                 # epilogues of mv_gemm this kernel does not have
+        assert gr(epi=epi) == E_ARG, epi
+    assert gr(epi=1, bias=None) == E_ARG and gr(epi=3, r=None) == E_ARG and gr(epi=3, rdt=5) == E_ARG and gr(epi=3, ldr=63) == E_ARG
+    ad = lambda **k: lib.mv_attn_decode(k.get("dt", BF16), k.get("q", P), k.get("ldq", 128), P, P, k.get("ldkv", 128), k.get("slots", P), k.get("lds", 8),
+                                        None, k.get("nk", P), k.get("max_nk", 8), P, k.get("ldo", 128), k.get("R", 2), 2, k.get("dh", 64),
+                                        k.get("nsplit", 1), k.get("ws", None), k.get("ws_bytes", 0), None)
+    assert ad(q=None) == E_ARG and ad(slots=None) == E_ARG and ad(nk=None) == E_ARG and ad(R=0) == E_ARG and ad(max_nk=0) == E_ARG and ad(nsplit=-1) == E_ARG
+    assert ad(dt=3) == E_DTYPE
+    assert ad(dh=48, ldq=96, ldkv=96, ldo=96) == E_SHAPE                                    # dh must divide 256
+    assert ad(dh=256, ldq=512, ldkv=512, ldo=512) == E_SHAPE and ad(dh=2, ldq=4, ldkv=4, ldo=4) == E_SHAPE      # dh <= 128, dh % 4
+    assert ad(ldq=127) == E_SHAPE and ad(ldkv=124) == E_SHAPE and ad(ldo=127) == E_SHAPE and ad(lds=0) == E_SHAPE
+    assert ad(nsplit=3) == E_WS                                                             # a forced split without a workspace
+    assert ad(nsplit=3, ws=P, ws_bytes=(3 * 2 * 2 * 66) * 4 - 4) == E_WS                    # ... or one float short of nsplit * R * A * (dh + 2)
+    tk = lambda **k: lib.mv_logprob_topk(k.get("x", P), k.get("ld", 40), k.get("R", 2), k.get("V", 40), k.get("k", 4), -1, k.get("vals", P), k.get("idx", P),
+                                         None, None)
+    assert tk(x=None) == E_ARG and tk(vals=None) == E_ARG and tk(idx=None) == E_ARG and tk(R=0) == E_ARG and tk(k=0) == E_ARG and tk(ld=39) == E_ARG
+    assert tk(k=17) == E_SHAPE                                                              # k <= 16
+    assert tk(k=5, V=4) == E_SHAPE                                                          # k <= V
+    er = lambda **k: lib.mv_embed_rows(k.get("dt", BF16), k.get("ids", P), P, P, k.get("E", P), P, P, P, P, k.get("out", P), k.get("ldo", 128), k.get("R", 2),
+                                       k.get("H", 128), k.get("V", 10), 8, k.get("ntype", 2), 1e-12, None)
+    assert er(ids=None) == E_ARG and er(E=None) == E_ARG and er(out=None) == E_ARG and er(R=0) == E_ARG and er(V=0) == E_ARG and er(ntype=0) == E_ARG
+    assert er(H=8196, ldo=8196) == E_SHAPE                                                  # H <= 8192
+    assert er(ldo=127) == E_SHAPE and er(dt=3) == E_DTYPE
+
+
 def test_host_mask_check_through_the_raw_abi(lib):
     """Real host work (the only entry point that computes on the CPU): ragged geometry, every family, 1-D masks, threads > samples."""
     out = C.c_longlong(0)
