@@ -256,7 +256,10 @@ int mv_attn_dropmask(float p_drop, unsigned long long drop_key, int B, int L, in
 
 /* dqkv [B*L,3H] from dctx [B*L,H]; `delta` is a [B,A,L] f32 scratch (rowsum(dctx*ctx)).  dtype (MV_F32, MV_BF16 or
  * MV_F16) is the encoding of qkv, ctx, dctx and dqkv alike.  qlim (nullable): as in mv_attn_fwd; the dctx rows past a sample's
- * limit are ignored (taken as zero) and their dQ rows are written as zeros. */
+ * limit are ignored (taken as zero) and their dQ rows are written as zeros.
+ * Alignment (16-bit MFMA path; MV_E_SHAPE otherwise): qkv and dctx 16 bytes, dqkv 8 bytes (mv_attn_fwd: qkv 16, ctx and ctx_bf16 8,
+ * dropbits 64).  ctx is not checked here: the kernels read it through a buffer descriptor in 16-byte pieces at element offsets that
+ * are multiples of 8, which needs the element alignment of the encoding only. */
 int mv_attn_bwd(int dtype, const void* qkv, const void* ctx, const void* dctx, const float* lse,
                 const uint32_t* bits, const uint8_t* tileinfo,
                 void* dqkv, float* delta, int B, int L, int A, int dh,

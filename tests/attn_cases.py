@@ -1,0 +1,788 @@
+"""Case generators, dispatch restatement, fp64 references, bounds and a torch stand-in of the attention sweep (csrc/mv_attn.hip).
+
+Plain module: nothing here touches the GPU or the HIP library.  tests/test_attn_fuzz_gpu.py runs the cases on the device,
+tests/test_attn_cases_cpu.py counts the branches they reach and validates the references and the bounds without a GPU.
+
+* every generator draws from np.random.RandomState(fixed + seed) and returns a dict; masks and tensors are rebuilt from the dict
+  alone, so a cfg printed by a failing assertion reproduces the case;
+* the dispatch restatement works from the DENSE mask (never from the kernel's tileinfo) and names, per block / wave / tile of the
+  three MFMA kernels, the path the kernel source takes;
+* the references are plain torch in float64 (CPU or device tensors) and call no kernel of this project.  The backward reference
+  restates the kernel's contract -- dQ, dK, dV, delta as functions of (qkv, ctx_in, dctx, lse_in, mask, keep-bits) -- so that the
+  backward can be fed statistics that do not come from the forward kernel;
+* the bounds are first-order error terms of the arithmetic the kernels do (see fwd_bounds / bwd_bounds), times ONE safety factor
+  SAFETY; nothing in them is fitted to a kernel's output.
+"""
+import math
+from collections import Counter
+
+import numpy as np
+import torch
+
+from rowops_cases import BF16, DT, F16, F16_SUBNORMAL_HALF_ULP, F32, U16, U32, f32r, out16_bound, sum_bound  # noqa: F401
+
+# ---- constants of csrc/mv_attn.hip and include/medvill.h (tests/test_attn_cases_cpu.py parses the same numbers from the sources) ----
+FWD_NS, DQ_NS, DKV_NS = 3, 4, 4
+MASK_ADD = -10000.0
+MAX_T = 64                    # mv_mask_pack / mv_mask_build: T = ceil(L / 64) <= 64
+MFMA_DH = 64
+VALU_MAX_DH = 128
+FAMILY_ID = {"full": 0, "s2s": 1, "bar": 2, "noncross": 3, "1d": 4}
+PACKABLE = ("full", "s2s", "1d")
+
+LENGTHS = (1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 192, 193, 257, 321, 577)
+VALU_DH = (8, 32, 64, 96, 128)
+VALUE_SETS = ("unit", "peaky", "rising", "falling", "tail")
+DSCALES = (2.0 ** -6, 1.0, 2.0 ** 6)
+DENSE_KINDS = ("random", "random2d", "holes", "split", "splitrev", "deadrow", "raggedones")
+QLIM_VALUES = (0, 1, 32, 33, 64, 128)
+PLANES = (8, 12, 16)
+
+# unit roundoff of an OPERAND rounded to the encoding (P, dS): half an ulp relative to the value.  (Stores go through
+# rowops_cases.out16_bound, which states bf16's as 2^-9 of |value| + row maximum.)
+UOP = {BF16: 2.0 ** -8, F16: 2.0 ** -11, F32: 2.0 ** -24}
+SAFETY = 2.0                  # the one factor over the first-order terms (second-order terms, ties, the order of the sums)
+F32_TOL = dict(ctx=1e-5, lse=1e-4, grad=1e-5, ctx_dead=1e-3, lse_dead=2e-3, grad_dead=1e-3)   # tests/test_kernels_gpu.py
+G_ROWS = 3                    # guard rows before and after every output of the sweep
+
+
+# =====================================================================================================================
+# dropout constants (attn_thr16 / attn_inv_keep)
+# =====================================================================================================================
+def drop_thr(p, planes):
+    full = 1 << planes
+    t = int(np.float32(p) * np.float32(full) + np.float32(0.5))
+    return min(max(t, 1), full - 1)
+
+
+def inv_keep(p, planes):
+    if p <= 0:
+        return 1.0
+    full = float(1 << planes)
+    return f32r(np.float32(full) / (np.float32(full) - np.float32(drop_thr(p, planes))))
+
+
+# =====================================================================================================================
+# masks
+# =====================================================================================================================
+def family_rule(fam, n2, vl, L):
+    """bool [L, L] of one sample: the closed forms of mask_build_kernel"""
+    i = torch.arange(L).view(L, 1)
+    j = torch.arange(L).view(1, L)
+    if fam == "s2s":
+        return ((j < n2) | ((i >= n2) & (j >= n2) & (j <= i))).expand(L, L)
+    if fam == "bar":
+        return ((i < n2) | (j < n2) | (j <= i)).expand(L, L)
+    if fam == "noncross":
+        return ((i < n2) == (j < n2)).expand(L, L)
+    return (j < vl).expand(L, L)
+
+
+def dense_mask(cfg):
+    """bool [B, L, L]: the logical mask of the case (a 2-D mask broadcast over the queries)"""
+    B, L, m = cfg["B"], cfg["L"], cfg["mask"]
+    if m["kind"] == "family":
+        return torch.stack([family_rule(f, n2, vl, L) for f, n2, vl in zip(m["fam"], m["n2"], m["vl"])]).contiguous()
+    rs = np.random.RandomState(77000 + cfg["seed"])
+    T = (L + 63) // 64
+    kind = m["kind"]
+    if kind == "random":
+        a = rs.rand(B, L, L) < 0.6
+        a[:, :, 0] = True
+    elif kind == "random2d":
+        r = rs.rand(B, L) < 0.6
+        r[:, 0] = True
+        a = np.broadcast_to(r[:, None, :], (B, L, L)).copy()
+    elif kind == "holes":                     # whole tiles zeroed in the middle of rows; key tile 0 stays visible for every row
+        a = np.ones((B, L, L), bool)
+        for b in range(B):
+            for tq in range(T):
+                for tk in range(1, T):
+                    u = rs.rand()
+                    if u < 0.5 and not (tk == T - 1 and tq == 0):
+                        a[b, tq * 64:(tq + 1) * 64, tk * 64:(tk + 1) * 64] = False
+                    elif u < 0.7:
+                        blk = a[b, tq * 64:(tq + 1) * 64, tk * 64:(tk + 1) * 64]
+                        blk &= rs.rand(*blk.shape) < 0.5
+    elif kind in ("split", "splitrev"):       # the two 64-row halves of a 128-row block see different classes for one key tile
+        a = np.ones((B, L, L), bool)
+        for b in range(B):
+            for xb in range((L + 127) // 128):
+                for tk in range(1, T):
+                    half = (tk + xb + (kind == "splitrev")) & 1
+                    r0 = xb * 128 + 64 * half
+                    blk = a[b, r0:r0 + 64, tk * 64:(tk + 1) * 64]
+                    if tk % 3 == 2:
+                        blk &= rs.rand(*blk.shape) < 0.5
+                    else:
+                        blk[...] = False
+    elif kind == "deadrow":                   # only key tile 0 is visible, and one query per sample sees nothing at all
+        a = np.zeros((B, L, L), bool)
+        a[:, :, :64] = True
+        for b in range(B):
+            a[b, int(rs.randint(0, L)), :] = False
+    elif kind == "raggedones":
+        a = np.ones((B, L, L), bool)
+    else:
+        raise ValueError(kind)
+    return torch.from_numpy(a)
+
+
+def mask_argument(cfg):
+    """what the case hands to mv_mask_pack (int64 [B, L, L] or [B, L]) or mv_mask_build (int32 [B, 3]) -> (how, tensor)"""
+    m = cfg["mask"]
+    if m["kind"] == "family" and m.get("via", "build") == "build":
+        return "build", torch.tensor([[FAMILY_ID[f], n2, vl] for f, n2, vl in zip(m["fam"], m["n2"], m["vl"])], dtype=torch.int32)
+    d = dense_mask(cfg)
+    if m["kind"] == "random2d" or (m["kind"] == "family" and all(f == "1d" for f in m["fam"])):
+        return "pack", d[:, 0, :].to(torch.int64).contiguous()
+    return "pack", d.to(torch.int64).contiguous()
+
+
+def pack_bits(dense):
+    """int32 [B, L, W] holding the uint32 words of mask_pack_kernel (bit j & 31 of word j >> 5 = mask[b, i, j])"""
+    B, L, _ = dense.shape
+    W = (L + 31) // 32
+    pad = torch.zeros((B, L, W * 32), dtype=torch.int64)
+    pad[:, :, :L] = dense.to(torch.int64)
+    w = (pad.view(B, L, W, 32) << torch.arange(32, dtype=torch.int64)).sum(-1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def tile_classes(dense):
+    """uint8 [B, T, T] as mask_tileinfo_kernel: 1 = every existing entry set (ragged tiles count their ncol columns and their existing
+    rows), 0 = every entry clear AND every existing row of the whole tile row sees some key (rows_ok), else 2"""
+    B, L, _ = dense.shape
+    T = (L + 63) // 64
+    out = torch.full((B, T, T), 2, dtype=torch.uint8)
+    for b in range(B):
+        for tq in range(T):
+            rows = dense[b, tq * 64:min(L, tq * 64 + 64)]
+            rows_ok = bool(rows.any(dim=1).all())
+            for tk in range(T):
+                blk = rows[:, tk * 64:min(L, tk * 64 + 64)]
+                if bool(blk.all()):
+                    out[b, tq, tk] = 1
+                elif not bool(blk.any()) and rows_ok:
+                    out[b, tq, tk] = 0
+    return out
+
+
+# =====================================================================================================================
+# row plans
+# =====================================================================================================================
+def row_plan(cfg):
+    """(Lv [B], Lq [B], cu or None): rows that exist, rows that are queries, packed row offsets"""
+    B, L = cfg["B"], cfg["L"]
+    Lv = list(cfg["lens"]) if cfg.get("lens") else [L] * B
+    Lq = [min(v, q) for v, q in zip(Lv, cfg["qlim"])] if cfg.get("qlim") else list(Lv)
+    cu = None
+    if cfg.get("lens"):
+        cu = [0]
+        for v in Lv:
+            cu.append(cu[-1] + v)
+    return Lv, Lq, cu
+
+
+# =====================================================================================================================
+# dispatch restatement (from the dense mask)
+# =====================================================================================================================
+def _ring_name(n):
+    return "ring%s" % ("9+" if n >= 9 else ("6-8" if n >= 6 else n))
+
+
+def att_block_map(order, nxb, A, B):
+    """flat block index -> (xb, head, b) as att_block() of mv_attn.hip (grid (nxb, A, B), x fastest)"""
+    nhb = A * B
+    out = []
+    for flat in range(nxb * nhb):
+        if order == 0:
+            xb = flat // nhb
+            pair = flat - xb * nhb
+        else:
+            full = (nhb >> 3) << 3
+            if flat < full * nxb:
+                x, k = flat & 7, flat >> 3
+                g = k // nxb
+                xb = k - g * nxb
+                pair = 8 * g + x
+            else:
+                r = flat - full * nxb
+                pair = full + r // nxb
+                xb = r - (pair - full) * nxb
+        out.append((xb, pair % A, pair // A))
+    return out
+
+
+def dropmask_block_map(nblocks, nbh):
+    """thread block -> logical block of attn_dropmask_kernel: spread when the grid divides into the (sample, head) pairs"""
+    per = nblocks // nbh
+    if per * nbh == nblocks:
+        return [(i % nbh) * per + i // nbh for i in range(nblocks)]
+    return list(range(nblocks))
+
+
+def dispatch(cfg, dense=None):
+    """Counter of the named paths the three MFMA kernels take on this case"""
+    c = Counter()
+    if cfg["path"] != "mfma":
+        c["valu:%s:dh%d" % (cfg["enc"], cfg["dh"])] += 1
+        return c
+    dense = dense_mask(cfg) if dense is None else dense
+    cls_all = tile_classes(dense).numpy()
+    B, L, drop = cfg["B"], cfg["L"], cfg["p"] > 0
+    T = (L + 63) // 64
+    Lv_, Lq_, cu = row_plan(cfg)
+    c["plan:packed" if cu else "plan:padded"] += 1
+    if cfg.get("qlim"):
+        c["plan:qlim"] += 1
+    if drop:                                  # attn_dropmask_kernel: blocks of 256 words spread over the pairs, or as they come
+        nblocks = (cfg["A"] * B * ((L + 31) // 32) * ((L + 63) // 64) * 32 + 255) // 256
+        c["dropmask:spread" if dropmask_block_map(nblocks, cfg["A"] * B) != list(range(nblocks)) else "dropmask:identity"] += 1
+    nhb = cfg["A"] * B
+    if cfg.get("order", 0) == 1:
+        c["order1:groups" if nhb >= 8 else "order1:no_group"] += 1
+        if nhb % 8:
+            c["order1:remainder"] += 1
+    for b in range(B):
+        cls, Lv, Lq = cls_all[b], Lv_[b], Lq_[b]
+        nkt, nqt = (Lv + 63) // 64, (Lq + 63) // 64
+        for xb in range((L + 127) // 128):
+            r0, ta = xb * 128, (xb * 128) >> 6
+            rows2 = [t for t in (ta, ta + 1) if t < T]
+            # ---- forward and dQ: queries on the rows, key tiles walked
+            need = [tk for tk in range(T) if any(cls[t, tk] != 0 for t in rows2)]
+            walk = [tk for tk in need if tk < nkt]
+            for kern, exits in (("fwd", r0 >= Lq), ("dq", r0 >= Lv)):
+                if exits:
+                    c[kern + ":block_exit"] += 1
+                    continue
+                if kern == "dq" and r0 >= Lq:
+                    c["dq:zero_fill_block"] += 1
+                    continue
+                c["%s:%s" % (kern, _ring_name(len(walk)))] += 1
+                if walk and walk != list(range(walk[0], walk[-1] + 1)):
+                    c[kern + ":need_holes"] += 1
+                for w in range(4):
+                    q0 = r0 + 32 * w
+                    if q0 >= Lq:
+                        c[kern + ":wave_off"] += 1
+                        continue
+                    if kern == "dq" and Lq < min(q0 + 32, Lv):
+                        c["dq:zero_rows_in_wave"] += 1
+                    tw = min(q0 >> 6, T - 1)
+                    for tk in walk:
+                        k = int(cls[tw, tk])
+                        ragged = tk * 64 + 64 > Lv
+                        if k == 0:
+                            c[kern + ":cls0_needed"] += 1
+                        elif kern == "fwd":
+                            plain = k == 1 and not ragged
+                            if k == 1 and ragged:
+                                c["fwd:cls1_demoted_ragged"] += 1
+                            c["fwd:%s%s" % ("plain" if plain else "masked", "_drop" if drop else "")] += 1
+                        else:
+                            c["dq:%s%s" % ("tail" if ragged else ("plain" if k == 1 else "masked"), "_drop" if drop else "")] += 1
+            # ---- dK/dV: keys on the rows, query tiles walked
+            if r0 >= Lv:
+                c["dkv:block_exit"] += 1
+                continue
+            need = [tq for tq in range(T) if any(cls[tq, t] != 0 for t in rows2)]
+            walk = [tq for tq in need if tq < nqt]
+            c["dkv:%s" % _ring_name(len(walk))] += 1
+            if walk and walk != list(range(walk[0], walk[-1] + 1)):
+                c["dkv:need_holes"] += 1
+            for w in range(4):
+                k0 = r0 + 32 * w
+                if k0 >= Lv:
+                    c["dkv:wave_off"] += 1
+                    continue
+                tw = min(k0 >> 6, T - 1)
+                for tq in walk:
+                    k = int(cls[tq, tw])
+                    if k == 0:
+                        c["dkv:cls0_needed"] += 1
+                    else:
+                        c["dkv:%s%s" % ("plain" if k == 1 else "masked", "_drop" if drop else "")] += 1
+    return c
+
+
+BRANCHES = tuple(
+    ["fwd:block_exit", "fwd:wave_off", "fwd:cls0_needed", "fwd:need_holes", "fwd:cls1_demoted_ragged"]
+    + ["fwd:%s%s" % (a, d) for a in ("plain", "masked") for d in ("", "_drop")]
+    + ["dq:block_exit", "dq:zero_fill_block", "dq:wave_off", "dq:cls0_needed", "dq:need_holes", "dq:zero_rows_in_wave"]
+    + ["dq:%s%s" % (a, d) for a in ("plain", "masked", "tail") for d in ("", "_drop")]
+    + ["dkv:block_exit", "dkv:wave_off", "dkv:cls0_needed", "dkv:need_holes"]
+    + ["dkv:%s%s" % (a, d) for a in ("plain", "masked") for d in ("", "_drop")]
+    + ["%s:%s" % (k, r) for k in ("fwd", "dq", "dkv") for r in ("ring1", "ring2", "ring3", "ring4", "ring5", "ring9+")]
+    + ["plan:packed", "plan:padded", "plan:qlim", "order1:groups", "order1:no_group", "order1:remainder", "dropmask:spread", "dropmask:identity"])
+
+
+# =====================================================================================================================
+# generators
+# =====================================================================================================================
+def _boundary_values(L):
+    """n2 / vl candidates: 1, a 32 boundary, a 64 boundary, one past it, L"""
+    c = [1, L]
+    for base in (32, 64, 128, 192):
+        c += [v for v in (base, base + 1) if v <= L]
+    return sorted(set(c))
+
+
+def _family_mask(rs, L, fams):
+    n2, vl = [], []
+    cand = _boundary_values(L)
+    for f in fams:
+        v = cand[int(rs.randint(len(cand)))]
+        n = cand[int(rs.randint(len(cand)))]
+        if f in ("full", "1d"):
+            n = min(n, v)
+        if f == "s2s":
+            v = max(v, n)              # the text follows the n2 image positions
+        n2.append(int(n))
+        vl.append(int(v))
+    return dict(kind="family", fam=list(fams), n2=n2, vl=vl)
+
+
+_BA = ((1, 1), (2, 2), (3, 3), (5, 3), (1, 2), (2, 1), (3, 1), (5, 1), (3, 2), (1, 3))      # (B, A): B.A = 9 and 15 included, and < 8
+
+
+def mfma_case(seed):
+    """families through mv_mask_build (every third case through mv_mask_pack), every length, plan, value set and encoding in turn"""
+    rs = np.random.RandomState(52000 + seed)
+    L = LENGTHS[seed % len(LENGTHS)]
+    B, A = _BA[(seed // 3) % len(_BA)]
+    if L >= 321:
+        B, A = min(B, 2), A
+    enc, ctx2 = ((BF16, False), (F16, False), (F16, True))[(seed // 2) % 3]
+    plan = ("padded", "packed", "qlim", "packed+qlim")[(seed // 5) % 4]
+    fam_pool = {"padded": ("full", "s2s", "bar", "noncross", "1d"), "packed": PACKABLE, "qlim": ("full", "s2s"), "packed+qlim": ("full", "s2s")}[plan]
+    if seed % 4 == 3 and plan != "padded":
+        fams = [fam_pool[int(rs.randint(len(fam_pool)))] for _ in range(B)]          # mixed batch
+        fams = ["full" if f == "1d" else f for f in fams]
+    else:
+        fams = [fam_pool[(seed // 7 + seed) % len(fam_pool)]] * B
+    mask = _family_mask(rs, L, fams)
+    mask["via"] = "pack" if (seed % 3 == 2 or fams[0] == "1d") else "build"
+    cfg = dict(seed=seed, path="mfma", enc=enc, ctx2=ctx2, B=B, L=L, A=A, dh=MFMA_DH, mask=mask, p=(0.0, 0.1)[(seed // 4 + seed) % 2], planes=16, order=0,
+               vals=VALUE_SETS[(seed + seed // 15) % len(VALUE_SETS)], dscale=DSCALES[(seed // 2 + seed // 15) % 3], zero_dctx=seed % 3 == 0)
+    if plan.startswith("packed"):
+        pool = [v for v in (1, 33, 64, 65, L) if v <= L]
+        cfg["lens"] = [int(min(mask["vl"][b], L)) if rs.rand() < 0.5 else int(pool[int(rs.randint(len(pool)))]) for b in range(B)]
+        for b in range(B):                    # a packed sample's length is its descriptor's vl
+            mask["vl"][b] = cfg["lens"][b]
+            if mask["fam"][b] == "s2s":
+                mask["n2"][b] = min(mask["n2"][b], cfg["lens"][b])
+    if plan.endswith("qlim"):
+        lv = cfg.get("lens", [L] * B)
+        pool = [v for v in QLIM_VALUES if v <= L] + [L]
+        cfg["qlim"] = [int(lv[b]) if rs.rand() < 0.25 else int(pool[(seed + b) % len(pool)]) for b in range(B)]
+    return cfg
+
+
+def dense_case(seed):
+    """dense masks through mv_mask_pack at the lengths where their tile structure exists"""
+    rs = np.random.RandomState(53000 + seed)
+    kind = DENSE_KINDS[seed % len(DENSE_KINDS)]
+    Ls = {"random": (33, 100, 129, 257, 321), "random2d": (65, 193, 321), "holes": (257, 321, 577), "split": (193, 257, 577),
+          "splitrev": (193, 321, 577), "deadrow": (129, 193, 321), "raggedones": (33, 65, 129, 193, 577)}[kind]
+    L = Ls[(seed // len(DENSE_KINDS)) % len(Ls)]
+    B, A = ((2, 3), (1, 2), (3, 1), (2, 1))[(seed // 2) % 4]
+    if L == 577:
+        B, A = 2, 3                           # the largest case of the sweep
+    enc, ctx2 = ((BF16, False), (F16, True), (F16, False))[(seed // 3) % 3]
+    cfg = dict(seed=seed, path="mfma", enc=enc, ctx2=ctx2, B=B, L=L, A=A, dh=MFMA_DH, mask=dict(kind=kind), p=(0.0, 0.1)[(seed // 7 + seed) % 2], planes=16,
+               order=0, vals=VALUE_SETS[(seed + seed // 5) % len(VALUE_SETS)], dscale=DSCALES[(seed + seed // 4) % 3], zero_dctx=seed % 4 == 1)
+    if kind in ("raggedones", "random2d") and seed % 2 == 0:      # rows beyond a packed length: every row sees every key, so the order is free
+        cfg["lens"] = [int(v) for v in rs.choice([v for v in (1, 33, 64, 65, L) if v <= L], size=B)]
+    return cfg
+
+
+def knob_case(seed):
+    """a small slice at attn_planes 8 / 12 and at attn_order 1 (whole groups of 8 + remainder, no whole group, exactly one group)"""
+    if seed < 6:
+        cfg = dense_case(100 + seed) if seed % 2 else mfma_case(100 + seed)
+        cfg.update(p=0.1, planes=(8, 12)[seed % 2 if seed < 4 else (seed + 1) % 2])
+        cfg["knob"] = "planes"
+        return cfg
+    k = seed - 6
+    B, A, L = ((3, 3, 193), (5, 3, 129), (2, 3, 257), (3, 2, 321), (4, 2, 129), (5, 1, 65), (3, 3, 65), (1, 2, 577))[k % 8]
+    kind = ("random", "holes", "raggedones", "split")[k % 4] if L >= 193 else ("random", "raggedones")[k % 2]
+    if kind == "holes" and L < 257:
+        kind = "random"
+    cfg = dict(seed=900 + k, path="mfma", enc=(BF16, F16)[k % 2], ctx2=False, B=B, L=L, A=A, dh=MFMA_DH, mask=dict(kind=kind), p=(0.0, 0.1)[k % 2],
+               planes=16, order=1, vals=VALUE_SETS[k % len(VALUE_SETS)], dscale=1.0, zero_dctx=False, knob="order")
+    return cfg
+
+
+def valu_case(seed):
+    """the VALU kernels: f32 at impl 0, bf16 / f16 at impl 1, every dh, L <= 129"""
+    rs = np.random.RandomState(54000 + seed)
+    dh = VALU_DH[seed % len(VALU_DH)]
+    enc = (F32, BF16, F16)[(seed // len(VALU_DH)) % 3]
+    L = (1, 31, 33, 64, 65, 100, 128, 129)[(seed + seed // 15) % 8]
+    B, A = ((2, 2), (1, 3), (3, 1))[seed % 3]
+    if seed % 2:
+        fam = ("full", "s2s", "bar", "noncross")[(seed // 2) % 4]
+        mask = _family_mask(rs, L, [fam] * B)
+        mask["via"] = "build"
+    else:
+        mask = dict(kind=("random", "deadrow", "random2d")[(seed // 2) % 3])
+    return dict(seed=seed, path="valu", enc=enc, ctx2=False, B=B, L=L, A=A, dh=dh, mask=mask, p=(0.0, 0.1)[(seed // 3) % 2], planes=16, order=0,
+                vals=VALUE_SETS[(seed + seed // 5) % len(VALUE_SETS)], dscale=DSCALES[seed % 3], zero_dctx=seed % 4 == 0)
+
+
+N_MFMA, N_DENSE, N_KNOB, N_VALU = 60, 42, 14, 30
+
+
+def mfma_cases():
+    return [mfma_case(s) for s in range(N_MFMA)]
+
+
+def dense_cases():
+    return [dense_case(s) for s in range(N_DENSE)]
+
+
+def knob_cases():
+    return [knob_case(s) for s in range(N_KNOB)]
+
+
+def valu_cases():
+    return [valu_case(s) for s in range(N_VALU)]
+
+
+def all_cases():
+    return mfma_cases() + dense_cases() + knob_cases() + valu_cases()
+
+
+def mask_cases():
+    """every distinct mask of the sweep (mask tests): the cfgs themselves"""
+    return mfma_cases() + dense_cases() + knob_cases()
+
+
+def case_id(c):
+    m = c["mask"]
+    name = m["kind"] if m["kind"] != "family" else "+".join(sorted(set(m["fam"])))
+    plan = ("pk" if c.get("lens") else "") + ("ql" if c.get("qlim") else "")
+    return f"{c['seed']}-{c['enc']}{'+b' if c['ctx2'] else ''}-L{c['L']}-B{c['B']}A{c['A']}-dh{c['dh']}-{name}-{plan or 'pad'}-p{c['p']}-{c['vals']}"
+
+
+# =====================================================================================================================
+# inputs
+# =====================================================================================================================
+def inputs(cfg):
+    """(qkv [B, L, 3H], dctx [B, L, H]) as CPU tensors already rounded to the case's encoding.  Rows beyond a packed length exist here
+    and are dropped by the caller."""
+    B, L, A, dh = cfg["B"], cfg["L"], cfg["A"], cfg["dh"]
+    H = A * dh
+    g = torch.Generator().manual_seed(61000 + cfg["seed"])
+    q = torch.randn((B, L, A, dh), generator=g)
+    k = torch.randn((B, L, A, dh), generator=g)
+    v = torch.randn((B, L, A, dh), generator=g)
+    d = torch.randn((B, L, H), generator=g)
+    Lv, _, _ = row_plan(cfg)
+    scale = 1.0 / math.sqrt(dh)
+    vals = cfg["vals"]
+    if vals == "peaky":                        # scores of standard deviation ~12
+        q, k = q * math.sqrt(12.0), k * math.sqrt(12.0)
+    elif vals in ("rising", "falling", "tail"):
+        gq = 4.0                               # component 0 of every query; component 0 of a key then adds gq * k0 * scale to its scores
+        q[..., 0] = gq
+        tile = (torch.arange(L) // 64).float().view(1, L, 1)
+        if vals == "rising":
+            k[..., 0] = 6.0 * tile / (gq * scale)          # +6 per key tile: every later tile raises the running maximum
+        elif vals == "falling":
+            k[..., 0] = -6.0 * tile / (gq * scale)
+        else:
+            k[..., 0] = 0.0
+            for b in range(B):
+                k[b, Lv[b] - 1, :, 0] = 20.0 / (gq * scale)     # the largest score sits on the last existing key
+    d = d * cfg["dscale"]
+    if cfg["zero_dctx"]:
+        d[:, ::5, :] = 0.0
+    qkv = torch.cat([q.reshape(B, L, H), k.reshape(B, L, H), v.reshape(B, L, H)], dim=-1)
+    dt = DT[cfg["enc"]]
+    return qkv.to(dt), d.to(dt)
+
+
+def cpu_keep(cfg):
+    """a Bernoulli keep mask [B, A, L, L] for the CPU checks (the device test decodes the kernel's own keep-bits instead)"""
+    if cfg["p"] <= 0:
+        return None
+    g = torch.Generator().manual_seed(62000 + cfg["seed"])
+    p = drop_thr(cfg["p"], cfg["planes"]) / float(1 << cfg["planes"])
+    return torch.rand((cfg["B"], cfg["A"], cfg["L"], cfg["L"]), generator=g) >= p
+
+
+# =====================================================================================================================
+# fp64 references
+# =====================================================================================================================
+def _heads(x, A):
+    B, L, H = x.shape
+    return x.view(B, L, A, H // A).permute(0, 2, 1, 3)
+
+
+def _unheads(x):
+    B, A, L, dh = x.shape
+    return x.permute(0, 2, 1, 3).reshape(B, L, A * dh)
+
+
+def scores(qkv64, dense, A, Lv):
+    """(s [B, A, L, L] fp64 with the -10000 additive mask and -inf on keys that do not exist, q, k, v [B, A, L, dh])"""
+    B, L, H3 = qkv64.shape
+    H = H3 // 3
+    q, k, v = (_heads(t, A) for t in qkv64.split(H, dim=-1))
+    s = q @ k.transpose(-1, -2) / math.sqrt(H // A) + (~dense.to(qkv64.device))[:, None].double() * MASK_ADD
+    j = torch.arange(L, device=qkv64.device).view(1, 1, 1, L)
+    lv = torch.as_tensor(Lv, device=qkv64.device).view(B, 1, 1, 1)
+    return s.masked_fill(j >= lv, -math.inf), q, k, v
+
+
+def ref_forward(qkv64, dense, A, Lv, keep=None, ikeep=1.0):
+    """-> dict(ctx [B, L, H], lse [B, A, L], p, pd [B, A, L, L], s, q, k, v).  Rows that are no queries are the caller's to ignore."""
+    s, q, k, v = scores(qkv64, dense, A, Lv)
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - lse.unsqueeze(-1))
+    pd = p if keep is None else p * keep.to(p.device).double() * ikeep
+    return dict(ctx=_unheads(pd @ v), lse=lse, p=p, pd=pd, s=s, q=q, k=k, v=v)
+
+
+def ref_backward(qkv64, ctx_in64, dctx64, lse_in64, dense, A, Lv, Lq, keep=None, ikeep=1.0):
+    """The backward's contract: P = exp(s - lse_in), delta = sum_d dctx . ctx_in, dS = P (keep inv_keep dP - delta) scale; rows that are
+    no queries contribute nothing and get a zero dQ.  -> dict(dq, dk, dv [B, L, H], delta [B, A, L], and the intermediates)"""
+    B, L, _ = qkv64.shape
+    dev = qkv64.device
+    s, q, k, v = scores(qkv64, dense, A, Lv)
+    qrow = (torch.arange(L, device=dev).view(1, L) < torch.as_tensor(Lq, device=dev).view(B, 1))       # [B, L]
+    qm = qrow.view(B, 1, L, 1)
+    lse = torch.where(qrow.view(B, 1, L), lse_in64, torch.zeros_like(lse_in64))
+    p = torch.where(qm, torch.exp(s - lse.unsqueeze(-1)), torch.zeros_like(s))
+    do = torch.where(qm, _heads(dctx64, A), torch.zeros((), dtype=torch.float64, device=dev))
+    o = torch.where(qm, _heads(ctx_in64, A), torch.zeros((), dtype=torch.float64, device=dev))
+    delta = (do * o).sum(-1)
+    kf = 1.0 if keep is None else keep.to(dev).double() * ikeep
+    dp = (do @ v.transpose(-1, -2)) * kf
+    scale = 1.0 / math.sqrt(q.shape[-1])
+    ds = p * (dp - delta.unsqueeze(-1)) * scale
+    pd = p * kf
+    return dict(dq=_unheads(ds @ k), dk=_unheads(ds.transpose(-1, -2) @ q), dv=_unheads(pd.transpose(-1, -2) @ do), delta=delta,
+                p=p, pd=pd, ds=ds, dp=dp, do=do, o=o, q=q, k=k, v=v, s=s, lse=lse, qm=qm)
+
+
+# =====================================================================================================================
+# bounds (16-bit MFMA kernels): per element, first-order terms x SAFETY
+# =====================================================================================================================
+def _score_err(s, q, k, stat):
+    """relative error of one probability exp(s - stat) computed in f32: the 64 (dh) f32 products of the score, the f32 arithmetic of the
+    exponent on magnitudes |s| and |stat| (product with the scale, mask add, subtraction: 4 roundings), one exp2 ulp and the scale's own
+    rounding.  For a fully masked row |s| ~ 1e4, which is the ulp(14427) term of tests/test_kernels_gpu.py::test_attention_fwd_bwd."""
+    dh = q.shape[-1]
+    sabs = (q.abs() @ k.abs().transpose(-1, -2)) / math.sqrt(dh)
+    sfin = torch.where(torch.isfinite(s), s.abs(), torch.zeros_like(s))
+    return sum_bound(dh, sabs) + 4.0 * U32 * (sfin + stat.abs().unsqueeze(-1)) + 4.0 * U32
+
+
+def fwd_bounds(r, enc, Lv, ikeep=1.0, store=None):
+    """ctx [B, L, H] and lse [B, A, L] bounds from the reference's intermediates r = ref_forward(...):
+      ctx: P rounded to 16 bits before P.V            UOP sum_k pd_k |v_kd|          (f16: + 2^-25 inv_keep sum_k |v_kd|, subnormal P)
+           score / exponent error e_k of p_k            sum_k pd_k e_k |v_kd|
+           the normaliser's relative error rho          rho sum_k pd_k |v_kd|,  rho = sum_k p_k e_k + 2 (Lv + 64) 2^-24
+           the f32 accumulation of Lv terms             2 Lv 2^-24 sum_k pd_k |v_kd|
+           plus the 16-bit store (out16_bound over the head's dh values); the sum times SAFETY: each term is attained, not merely
+           approached, when one key dominates a row or a value rounds to zero, so a correct kernel may reach 1 / SAFETY of the bound
+      lse: SAFETY (rho + 4 2^-24 (max|s| + |lse|) + 4 2^-24)"""
+    s, p, pd, q, k, v, lse = r["s"], r["p"], r["pd"], r["q"], r["k"], r["v"], r["lse"]
+    B, A, L, dh = q.shape
+    vis = s >= (lse.unsqueeze(-1) - 150.0)                                       # keys that can matter to the row
+    smax = torch.where(vis, s.abs(), torch.zeros_like(s)).amax(-1)
+    e = _score_err(s, q, k, smax)
+    n = float(max(Lv))
+    rho = (p * e).sum(-1) + 2.0 * (n + 64.0) * U32
+    pv = pd @ v.abs()
+    first = UOP[enc] * pv + (pd * e) @ v.abs() + rho.unsqueeze(-1) * pv + sum_bound(n, pv)
+    if enc == F16:
+        j = torch.arange(L, device=s.device).view(1, 1, L, 1) < torch.as_tensor(Lv, device=s.device).view(B, 1, 1, 1)
+        first = first + F16_SUBNORMAL_HALF_ULP * ikeep * (v.abs() * j).sum(2, keepdim=True)
+    ctx_h = _heads(r["ctx"], A)
+    b_ctx = _unheads(SAFETY * (first + out16_bound(ctx_h, store or enc, 0.0)))      # store: the second output's encoding (bf16 copy)
+    b_lse = SAFETY * (rho + 4.0 * U32 * (smax + lse.abs()) + 4.0 * U32)
+    return b_ctx, b_lse
+
+
+def bwd_bounds(r, enc, Lv, ikeep=1.0):
+    """dq, dk, dv [B, L, H] and delta [B, A, L] bounds from r = ref_backward(...).  With e_k the probability's relative error (as in the
+    forward, against lse_in), E_dp = 2 dh 2^-24 sum_i |dO_i v_i| inv_keep, E_dl = 2 dh 2^-24 sum_i |dO_i ctx_i| (= the delta bound) and
+    E_t = 2 2^-24 (|dP| + |delta|) the rounding of dP inv_keep scale - delta scale:
+      dS error   a_qk = (UOP + e_qk) |dS_qk| + p_qk scale (E_dp + E_dl + E_t)          (f16: + 2^-25, subnormal dS)
+      dQ_qd: sum_k a_qk |k_kd| + 2 Lv 2^-24 sum_k |dS_qk| |k_kd|;   dK_kd: the same over q with |q_qd|
+      dV_kd: sum_q (UOP + e_qk) pd_qk |dO_qd| + 2 Lq 2^-24 sum_q pd_qk |dO_qd|          (f16: + 2^-25 inv_keep sum_q |dO_qd|)
+      plus the 16-bit store; the sum times SAFETY."""
+    s, p, pd, ds, dp, do, o, q, k, v, lse = (r[n] for n in ("s", "p", "pd", "ds", "dp", "do", "o", "q", "k", "v", "lse"))
+    B, A, L, dh = q.shape
+    scale = 1.0 / math.sqrt(dh)
+    n = float(max(Lv))
+    e = _score_err(s, q, k, lse) * r["qm"]
+    e = torch.where(torch.isfinite(e), e, torch.zeros_like(e))
+    b_delta = SAFETY * (sum_bound(dh, (do.abs() * o.abs()).sum(-1)) + 2.0 * U32 * r["delta"].abs()) + 1e-300
+    E_dp = sum_bound(dh, do.abs() @ v.abs().transpose(-1, -2)) * ikeep
+    E_dl = sum_bound(dh, (do.abs() * o.abs()).sum(-1)).unsqueeze(-1)
+    E_t = 2.0 * U32 * (dp.abs() + r["delta"].abs().unsqueeze(-1))
+    a = (UOP[enc] + e) * ds.abs() + p * scale * (E_dp + E_dl + E_t)
+    av = (UOP[enc] + e) * pd
+    if enc == F16:
+        exist = torch.isfinite(s) & r["qm"]
+        a = a + F16_SUBNORMAL_HALF_ULP * exist
+        av = av + F16_SUBNORMAL_HALF_ULP * ikeep * exist
+    f_dq = a @ k.abs() + sum_bound(n, ds.abs() @ k.abs())
+    f_dk = a.transpose(-1, -2) @ q.abs() + sum_bound(n, ds.abs().transpose(-1, -2) @ q.abs())
+    f_dv = av.transpose(-1, -2) @ do.abs() + sum_bound(n, pd.transpose(-1, -2) @ do.abs())
+    out = {}
+    for name, f in (("dq", f_dq), ("dk", f_dk), ("dv", f_dv)):
+        store = out16_bound(_heads(r[name], A), enc, 0.0) if enc != F32 else U32 * _heads(r[name], A).abs()
+        out[name] = _unheads(SAFETY * (f + store))
+    out["delta"] = b_delta
+    return out
+
+
+def flat_bound(ref_h, enc, tol, cpu_err=0.0, floor=0.0):
+    """VALU kernels: the f32 tolerance of the fixed-shape tests relative to the row's largest magnitude (not below `floor`, which the
+    callers set to 1e-3 of the largest magnitude of the output, as rowops_cases.rowrel does: a row whose exact result is zero still
+    carries the cancellation error of its terms), never below 4 x the error plain f32 torch makes on the CPU on the same inputs;
+    16-bit encodings add their store (out16_bound)."""
+    tol = max(tol, 4.0 * cpu_err)
+    rowmax = ref_h.abs().amax(-1, keepdim=True).clamp_min(floor)
+    b = (tol * rowmax + 1e-300).expand_as(ref_h)
+    if enc == F32:
+        return b
+    return b + out16_bound(ref_h, enc, 0.0)
+
+
+def cpu_f32_errors(cfg, keep=None):
+    """What plain f32 torch on the CPU makes of the same inputs, against the same computation in fp64: dict(ctx, grad) relative to the
+    largest magnitude of the row (per head), lse absolute.  The VALU tolerances are never taken below 4 x these."""
+    A, dh, B, L = cfg["A"], cfg["dh"], cfg["B"], cfg["L"]
+    H = A * dh
+    qkv, dctx = inputs(cfg)
+    dense, ik = dense_mask(cfg), inv_keep(cfg["p"], cfg["planes"])
+    res = {}
+    for dt in (torch.float32, torch.float64):
+        x = qkv.to(dt).clone().detach().requires_grad_(True)
+        q, k, v = (_heads(t, A) for t in x.split(H, dim=-1))
+        sc = q @ k.transpose(-1, -2) / math.sqrt(dh) + (~dense)[:, None].to(dt) * MASK_ADD
+        pr = torch.softmax(sc, -1)
+        if keep is not None:
+            pr = pr * keep.to(dt) * ik
+        ctx = _unheads(pr @ v)
+        (ctx * dctx.to(dt)).sum().backward()
+        res[dt] = (ctx.detach().double(), torch.logsumexp(sc, -1).detach().double(), x.grad.double())
+
+    def rel(a, b):
+        a, b = _heads(a, A), _heads(b, A)
+        return float(((a - b).abs() / (b.abs().amax(-1, keepdim=True) + 1e-300)).max())
+    (c32, l32, g32), (c64, l64, g64) = res[torch.float32], res[torch.float64]
+    return dict(ctx=rel(c32, c64), lse=float((l32 - l64).abs().max()), grad=max(rel(g32[..., i * H:(i + 1) * H], g64[..., i * H:(i + 1) * H]) for i in range(3)))
+
+
+# =====================================================================================================================
+# torch stand-in of the tile-wise algorithm (CPU only: validates the bounds, and with `bug` shows they are not vacuous)
+# =====================================================================================================================
+BUGS = ("no_alpha", "tail_off_by_one", "mask_word_off_by_one", "no_inv_keep", "delta_not_subtracted", "dk_dv_swapped")
+
+
+def _r16(x, enc):
+    return x.to(DT[enc]).float()
+
+
+def standin_forward(qkv, dense, A, Lv, Lq, enc, keep=None, ikeep=1.0, bug=None, store=None):
+    """online softmax over 64-key tiles in f32, P rounded to the encoding before P.V, 16-bit stores -> (ctx [B, L, H], lse [B, A, L])"""
+    B, L, H3 = qkv.shape
+    H = H3 // 3
+    dh = H // A
+    q, k, v = (_heads(t.float(), A) for t in qkv.split(H, dim=-1))
+    c2 = np.float32(1.0 / math.sqrt(dh)) * np.float32(1.4426950408889634)
+    m = torch.full((B, A, L), -math.inf)
+    lsum = torch.zeros((B, A, L))
+    o = torch.zeros((B, A, L, dh))
+    lv = torch.as_tensor(Lv).view(B, 1, 1, 1)
+    if bug == "tail_off_by_one" and L % 64:       # the key at L is a zero-filled row; its mask bit is set only where the tile is read as all ones
+        k, v = (torch.cat([t, torch.zeros((B, A, 1, dh))], dim=2) for t in (k, v))
+        dense = torch.cat([dense, dense[:, :, (L - 1) // 64 * 64:].all(-1, keepdim=True)], dim=-1)
+        keep = None if keep is None else torch.cat([keep, torch.ones_like(keep[..., :1])], dim=-1)
+        L = L + 1
+    for k0 in range(0, max(Lv), 64):
+        k1 = min(k0 + 64, L)
+        msk = dense[:, None, :, k0:k1]
+        if bug == "mask_word_off_by_one" and k1 - k0 > 32:      # the tile's second word taken from one word further on
+            msk = msk.clone()
+            src = dense[:, None, :, k0 + 64:k0 + 96]
+            msk[..., 32:32 + src.shape[-1]] = src[..., :k1 - k0 - 32]
+            msk[..., 32 + src.shape[-1]:] = True
+        st = (q @ k[:, :, k0:k1].transpose(-1, -2)) * float(c2) + (~msk).float() * float(np.float32(MASK_ADD) * np.float32(1.4426950408889634))
+        j = torch.arange(k0, k1).view(1, 1, 1, -1)
+        gone = (j > lv) if bug == "tail_off_by_one" else (j >= lv)
+        if bug == "tail_off_by_one":                             # the key at Lv is read as a zero-filled row
+            st = torch.where(j == lv, (~msk).float() * float(np.float32(MASK_ADD) * np.float32(1.4426950408889634)), st)
+        st = st.masked_fill(gone, -math.inf)
+        mn = torch.maximum(m, st.amax(-1))
+        alpha = torch.exp2(m - mn)
+        alpha = torch.where(torch.isnan(alpha), torch.zeros_like(alpha), alpha)
+        pt = torch.exp2(st - mn.unsqueeze(-1))
+        pt = torch.where(torch.isnan(pt), torch.zeros_like(pt), pt)
+        if bug == "no_alpha":
+            alpha = torch.ones_like(alpha)
+        lsum = lsum * alpha + pt.sum(-1)
+        if keep is not None:
+            pt = pt * keep[:, :, :, k0:k1].float()
+        vt = v[:, :, k0:k1]
+        if bug == "tail_off_by_one":
+            vt = vt * (torch.arange(k0, k1).view(1, 1, -1, 1) < torch.as_tensor(Lv).view(B, 1, 1, 1))
+        o = o * alpha.unsqueeze(-1) + _r16(pt, enc) @ vt
+        m = mn
+    inv = (1.0 if bug == "no_inv_keep" else float(np.float32(ikeep))) / lsum
+    ctx = _unheads(o * inv.unsqueeze(-1)).to(DT[store or enc])           # store: the encoding of the second (bf16) context output
+    lse = (m + torch.log2(lsum)) * float(np.float32(0.6931471805599453))
+    return ctx, lse
+
+
+def standin_backward(qkv, ctx_in, dctx, lse_in, dense, A, Lv, Lq, enc, keep=None, ikeep=1.0, bug=None, store=None):
+    """f32 scores and exponentials against lse_in, dS and P rounded to the encoding before their products, 16-bit stores
+    -> (dq, dk, dv [B, L, H] in the encoding, delta [B, A, L] f32).  Of BUGS only the last three exist in a backward; the others are
+    faults of the forward's tile walk, under which this function is the honest backward."""
+    assert bug is None or bug in BUGS
+    B, L, H3 = qkv.shape
+    H = H3 // 3
+    dh = H // A
+    q, k, v = (_heads(t.float(), A) for t in qkv.split(H, dim=-1))
+    qrow = torch.arange(L).view(1, L) < torch.as_tensor(Lq).view(B, 1)
+    qm = qrow.view(B, 1, L, 1)
+    do = torch.where(qm, _heads(dctx.float(), A), torch.zeros(()))
+    o = torch.where(qm, _heads(ctx_in.float(), A), torch.zeros(()))
+    lse = torch.where(qrow.view(B, 1, L), lse_in.float(), torch.zeros(()))
+    scale = float(np.float32(1.0 / math.sqrt(dh)))
+    s = (q @ k.transpose(-1, -2)) * scale + (~dense)[:, None].float() * MASK_ADD
+    j = torch.arange(L).view(1, 1, 1, L)
+    p = torch.exp(s - lse.unsqueeze(-1)).masked_fill(j >= torch.as_tensor(Lv).view(B, 1, 1, 1), 0.0) * qm
+    delta = (do * o).sum(-1)
+    kf = torch.ones(()) if keep is None else keep.float() * (1.0 if bug == "no_inv_keep" else float(np.float32(ikeep)))
+    dp = (do @ v.transpose(-1, -2)) * kf
+    dl = torch.zeros_like(delta) if bug == "delta_not_subtracted" else delta
+    ds = _r16(p * (dp - dl.unsqueeze(-1)) * scale, enc)
+    pd = _r16(p * kf, enc)
+    dq, dk, dv = ds @ k, ds.transpose(-1, -2) @ q, pd.transpose(-1, -2) @ do
+    if bug == "dk_dv_swapped":
+        dk, dv = dv, dk
+    return tuple(_unheads(t).to(DT[store or enc]) for t in (dq, dk, dv)) + (delta,)
+
+
+def worst_ratio(got, ref, bound, rows=None):
+    """largest |got - ref| / bound, over the rows selected by the bool mask `rows` (broadcast against ref) -> (ratio, flat index)"""
+    err = (got.double() - ref).abs()
+    r = err / bound
+    r = torch.where(torch.isnan(r), torch.full_like(r, math.inf), r)
+    r = torch.where(err == 0, torch.zeros_like(r), r)                      # an exact result meets any bound, a zero one included
+    if rows is not None:
+        r = torch.where(rows.expand_as(r), r, torch.zeros_like(r))
+    if r.numel() == 0:
+        return 0.0, -1
+    i = int(r.argmax())
+    return float(r.flatten()[i]), i

@@ -73,6 +73,76 @@ def test_attention_rejects(lib):
     assert lib.mv_attn_dropmask(0.1, 1, 2, 64, 2, None, None, None) == E_ARG
 
 
+def test_attention_entry_points_reject_before_any_launch(lib):
+    """Every reject path of mv_attn_fwd / mv_attn_bwd / mv_attn_dropmask / mv_mask_pack / mv_mask_build.  The outputs are real, NaN-filled
+    host buffers, compared afterwards: the host side of a launcher that returns an error has written nothing.  (That nothing was
+    launched is the error code's word, as everywhere in this file: a kernel could not write host memory anyway.)  mv_attn_bwd does not
+    check the alignment of ctx (include/medvill.h says why), so that reject exists for the forward only."""
+    def aligned(n, dt, fill):                # 64-byte aligned, whatever the allocator returns
+        raw = np.empty(n * np.dtype(dt).itemsize + 64, dtype=np.uint8)
+        a = raw[(-raw.ctypes.data) % 64:][:n * np.dtype(dt).itemsize].view(dt)
+        a[...] = fill
+        return a
+    nan = lambda n, dt=np.float32: aligned(n, dt, np.nan)
+    B, L, A = 2, 64, 2
+    ctx, ctx2, lse, dqkv, delta = nan(B * L * A * 64, np.float16), nan(B * L * A * 64, np.float16), nan(B * A * L), nan(B * L * 3 * A * 64, np.float16), nan(B * A * L)
+    bits, info, db = aligned(B * L * 2, np.uint32, 0x5A5A5A5A), aligned(B, np.uint8, 0xA5), aligned(B * A * 2 * 64, np.uint32, 0x3C3C3C3C)
+    outs = (ctx, ctx2, lse, dqkv, delta, bits, info, db)
+    before = [o.copy() for o in outs]
+    ptr = lambda a: a.ctypes.data
+    assert all(ptr(o) % 16 == 0 for o in (ctx, ctx2, dqkv)) and ptr(db) % 64 == 0
+
+    def fwd(dt=BF16, qkv=P, bits_=P, info_=P, ctx_=None, ctx2_=None, lse_=None, B_=B, L_=L, A_=A, dh=64, p=0.0, db_=None, cu=None, rows=0, qlim=None):
+        return lib.mv_attn_fwd(dt, qkv, bits_, info_, ptr(ctx) if ctx_ is None else ctx_, ctx2_, ptr(lse) if lse_ is None else lse_, B_, L_, A_, dh, p,
+                               db_, cu, rows, qlim, None)
+
+    def bwd(dt=BF16, qkv=P, ctx_=P, dctx=P, lse_=P, bits_=P, info_=P, dqkv_=None, delta_=None, B_=B, L_=L, A_=A, dh=64, p=0.0, db_=None, cu=None,
+            rows=0, qlim=None):
+        return lib.mv_attn_bwd(dt, qkv, ctx_, dctx, lse_, bits_, info_, ptr(dqkv) if dqkv_ is None else dqkv_, ptr(delta) if delta_ is None else delta_,
+                               B_, L_, A_, dh, p, db_, cu, rows, qlim, None)
+
+    for f in (fwd, bwd):
+        # 16-bit MFMA path
+        for dt in (BF16, F16):
+            assert f(dt=dt, dh=32) == E_SHAPE and f(dt=dt, dh=128) == E_SHAPE and f(dt=dt, dh=65) == E_SHAPE
+            assert f(dt=dt, cu=P, rows=0) == E_ARG and f(dt=dt, cu=P, rows=-1) == E_ARG and f(dt=dt, cu=P, rows=B * L + 1) == E_ARG
+            assert f(dt=dt, qkv=P + 8) == E_SHAPE and f(dt=dt, qkv=P + 2) == E_SHAPE
+        # dropout arguments
+        assert f(p=1.0, db_=ptr(db)) == E_ARG and f(p=1.5, db_=ptr(db)) == E_ARG and f(p=0.1) == E_ARG and f(dt=F32, p=0.1) == E_ARG
+        assert f(p=0.1, db_=ptr(db) + 32) == E_SHAPE and f(p=0.1, db_=ptr(db) + 4) == E_SHAPE
+        # encoding and path limits
+        assert f(dt=F32, cu=P, rows=B * L) == E_SHAPE and f(dt=F32, qlim=P) == E_SHAPE and f(dt=F32, dh=129) == E_SHAPE and f(dt=F32, dh=256) == E_SHAPE
+        assert f(dt=3) == E_DTYPE and f(dt=-1) == E_DTYPE
+        # null pointers and non-positive sizes
+        assert f(qkv=None) == E_ARG and f(bits_=None) == E_ARG and f(info_=None) == E_ARG
+        for k in ("B_", "L_", "A_", "dh"):
+            assert f(**{k: 0}) == E_ARG and f(**{k: -2}) == E_ARG
+    assert fwd(ctx_=ptr(ctx) + 4) == E_SHAPE and fwd(ctx_=ptr(ctx) + 2) == E_SHAPE
+    assert fwd(dt=F16, ctx2_=ptr(ctx2) + 4) == E_SHAPE
+    assert fwd(dt=BF16, ctx2_=ptr(ctx2)) == E_DTYPE and fwd(dt=F32, ctx2_=ptr(ctx2)) == E_DTYPE
+    assert bwd(dctx=P + 8) == E_SHAPE and bwd(dqkv_=ptr(dqkv) + 4) == E_SHAPE
+    assert bwd(ctx_=None) == E_ARG and bwd(dctx=None) == E_ARG and bwd(lse_=None) == E_ARG
+    assert lib.mv_attn_fwd(BF16, P, P, P, None, None, ptr(lse), B, L, A, 64, 0.0, None, None, 0, None, None) == E_ARG
+    assert lib.mv_attn_fwd(BF16, P, P, P, ptr(ctx), None, None, B, L, A, 64, 0.0, None, None, 0, None, None) == E_ARG
+    assert lib.mv_attn_bwd(BF16, P, P, P, P, P, P, None, ptr(delta), B, L, A, 64, 0.0, None, None, 0, None, None) == E_ARG
+    assert lib.mv_attn_bwd(BF16, P, P, P, P, P, P, ptr(dqkv), None, B, L, A, 64, 0.0, None, None, 0, None, None) == E_ARG
+    # keep-bit generator
+    dm = lambda p=0.1, B_=B, L_=L, A_=A, out=None: lib.mv_attn_dropmask(p, 7, B_, L_, A_, None, ptr(db) if out is None else out, None)
+    assert dm(p=0.0) == E_ARG and dm(p=-0.1) == E_ARG and dm(p=1.0) == E_ARG and dm(B_=0) == E_ARG and dm(L_=0) == E_ARG and dm(A_=-1) == E_ARG
+    assert lib.mv_attn_dropmask(0.1, 7, B, L, A, None, None, None) == E_ARG
+    assert dm(out=ptr(db) + 32) == E_SHAPE and dm(B_=64, L_=4096, A_=16) == E_SHAPE          # 32-bit hash counters / buffer offsets
+    # masks
+    for nd in (0, 1, 4, -1):
+        assert lib.mv_mask_pack(P, nd, B, L, ptr(bits), ptr(info), None) == E_SHAPE
+    for bad in ((None, P, P), (P, None, P), (P, P, None)):
+        assert lib.mv_mask_pack(bad[0], 3, B, L, bad[1], bad[2], None) == E_ARG and lib.mv_mask_build(bad[0], B, L, bad[1], bad[2], None) == E_ARG
+    for fn in (lambda b, l: lib.mv_mask_pack(P, 3, b, l, ptr(bits), ptr(info), None), lambda b, l: lib.mv_mask_build(P, b, l, ptr(bits), ptr(info), None)):
+        assert fn(0, L) == E_ARG and fn(-1, L) == E_ARG and fn(B, 0) == E_ARG and fn(B, -5) == E_ARG
+        assert fn(B, 64 * 64 + 1) == E_SHAPE and fn(1, 1 << 20) == E_SHAPE                    # T = ceil(L / 64) > 64
+    for o, b in zip(outs, before):
+        assert o.tobytes() == b.tobytes()
+
+
 def test_rowop_rejects(lib):
     assert lib.mv_layernorm_fwd(BF16, None, F32, P, P, P, None, P, P, 4, 128, 1e-12, None) == E_ARG
     assert lib.mv_layernorm_fwd(BF16, P, F32, P, P, P, None, P, P, 4, 130, 1e-12, None) == E_SHAPE          # H % 4
