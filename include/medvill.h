@@ -526,6 +526,37 @@ int mv_bce_multilabel(const float* logits, int ld, const float* target, const fl
                       void* dgrad, int d_dtype, int ldd, const float* grad_scale_dev, float grad_scale_host,
                       const float* loss_scale_dev, float* probs, float* counters, void* stream);
 
+/* ---- Report-generation fine-tuning (csrc/mv_lmloss.hip) ----------------------------------------------
+ * The masked-LM objective of the reference's BertForPreTrainingLossMask(tasks='report_generation') (Downstream_task/
+ * report_generation_and_vqa/sc/pytorch_pretrained_bert/model.py:998-1005,1043-1054, loss.py:12-48).  Additive entry points.
+ *
+ * logits f32 [U, ld] (ld >= V): one row per DISTINCT consumed position.  The prediction entries are stored in CSR form over those
+ * rows: row u owns entries row_ptr[u] .. row_ptr[u+1]-1 (row_ptr int32 [U+1], row_ptr[U] = n_entries); entry e has labels[e] (int32,
+ * 0 <= label < V), weights[e] (f32 >= 0) and sample[e] (int32, 0 <= sample < B).  Several entries may share a row, with equal or
+ * different labels.  label_smoothing in [0, 1]; with smoothing V >= 3, c = 1 - label_smoothing, s = f32(label_smoothing / (V-2)).
+ * mv_lm_loss_fwd: per row one pass (max, sum of exponentials, sum of the logits over columns 1..V-1, first argmax); per entry
+ *     entry_loss[e] = lse - z[label]                                                       (label_smoothing == 0; label 0 counts)
+ *                   = 0                                                                    (smoothing, label 0: ignored)
+ *                   = c log c + (V-2) s log s - c (z[t] - lse) - s ((zsum - z[t]) - (V-2) lse)     (smoothing; 0 log 0 = 0)
+ *     entry_hit[e] (int32, nullable) = argmax == label;  row_stat f32 [U, 2] = {max, sum exp(z - max)} for the backward.
+ * mv_lm_loss_select (one launch of one block, B <= 2048): per-sample sums of w * loss and of w in entry order (double, no atomics:
+ *     bitwise reproducible); keep[b] (int32 [B]) = 1 for the k samples with the smallest loss sums, ties to the lower sample index;
+ *     stats f32 [4] = {sum of kept loss sums / (kept weight sum + 1e-5), kept weight sum, kept sample count, entries of kept samples
+ *     with weight > 0 whose argmax equals the label}; *inv_denom = 1 / (kept weight sum + 1e-5).  k = 0: loss 0, nothing kept.
+ * mv_lm_loss_bwd: dlogits[u, c] = g S inv_denom sum over the row's entries with keep[sample] != 0 of w (Q softmax[c] - q[c]) for c < V
+ *     and 0 for V <= c < ldd (d_dtype f32 / bf16 / f16); q = the entry's target row (one-hot without smoothing; with it 0 in column 0,
+ *     c at the label, s elsewhere, and all zero for label 0), Q = its sum; g = *grad_dev, S = *loss_scale_dev (nullable = 1).  A row
+ *     without a kept entry of positive weight and mass is written as zeros and its logits are not read.
+ * U = 0 launches nothing.  Null pointers, negative counts, ld < V, V < 3 under smoothing: MV_E_ARG; ldd < V, B > 2048: MV_E_SHAPE.  */
+int mv_lm_loss_fwd(const float* logits, int ld, int U, int V, const int32_t* row_ptr, const int32_t* labels, int n_entries,
+                   double label_smoothing, float* entry_loss, int32_t* entry_hit, float* row_stat, void* stream);
+int mv_lm_loss_select(const float* entry_loss, const float* weights, const int32_t* sample, const int32_t* entry_hit, int n_entries,
+                      int B, int k, int32_t* keep, float* stats, float* inv_denom, void* stream);
+int mv_lm_loss_bwd(const float* logits, int ld, int U, int V, const int32_t* row_ptr, const int32_t* labels, const float* weights,
+                   const int32_t* sample, int n_entries, double label_smoothing, const float* row_stat, const int32_t* keep,
+                   const float* inv_denom, const float* grad_dev, const float* loss_scale_dev, void* dlogits, int d_dtype, int ldd,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

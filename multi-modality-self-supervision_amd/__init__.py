@@ -44,7 +44,8 @@ from .trainer import CXRBERT_Trainer, TrainStep  # noqa: F401
 from .retrieval import CXRBertForGeneration, CXRBertForRetrieval  # noqa: F401
 from .vqa import CXRBertForVQA  # noqa: F401
 from .classification import CXRBertForClassification  # noqa: F401
+from .report_finetune import CXRBertForReportFinetune  # noqa: F401
 from .image import ImageEncoder_cnn  # noqa: F401
-from . import beam, checkpoint, classification, data, dist, hip_ops, losses, optim, vqa  # noqa: F401
+from . import beam, checkpoint, classification, data, dist, hip_ops, losses, optim, report_finetune, vqa  # noqa: F401
 
-__all__ = ["Engine", "ModelConfig", "param_layout", "CXRBERT", "CXRBERT_Trainer", "TrainStep", "CXRBertForRetrieval", "CXRBertForGeneration", "CXRBertForVQA", "CXRBertForClassification", "ImageEncoder_cnn", "data"]
+__all__ = ["Engine", "ModelConfig", "param_layout", "CXRBERT", "CXRBERT_Trainer", "TrainStep", "CXRBertForRetrieval", "CXRBertForGeneration", "CXRBertForVQA", "CXRBertForClassification", "CXRBertForReportFinetune", "ImageEncoder_cnn", "data"]

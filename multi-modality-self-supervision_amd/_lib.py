@@ -87,6 +87,10 @@ PROTOTYPES = {
     "mv_tensor_sqnorms": [vp, sz, vp, i32, vp, i32, vp, vp, vp],
     "mv_bce_multilabel": [vp, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, f32, vp, vp, vp, vp],
     "mv_bertadam_step": [vp, vp, vp, vp, vp, vp, sz, vp, i32, vp, i32, vp, f64, f64, f64, f32, f32, f32, i32, i32, f64, i32, vp, vp],
+    # report-generation fine-tuning (csrc/mv_lmloss.hip)
+    "mv_lm_loss_fwd": [vp, i32, i32, i32, vp, vp, i32, f64, vp, vp, vp, vp],
+    "mv_lm_loss_select": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    "mv_lm_loss_bwd": [vp, i32, i32, i32, vp, vp, vp, vp, i32, f64, vp, vp, vp, vp, vp, vp, i32, i32, vp],
 }
 # include/medvill_debug.h: exported by libmedvill_hip_dbg.so only
 DEBUG_PROTOTYPES = {"mv_debug_set_knob": [i32, i32], "mv_debug_get_knob": [i32]}

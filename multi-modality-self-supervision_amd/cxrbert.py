@@ -659,6 +659,11 @@ class CXRBERT(nn.Module):
                 config = json.load(f)
         if state_dict is None:
             state_dict = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu")
+        if not any(k_.startswith("enc.") for k_ in state_dict) and any(k_.startswith(("encoder.", "txt_embeddings.", "cls.")) for k_ in state_dict):
+            # the downstream programs' fine-tune layout (finetune.py:338-339; CXRBertForReportFinetune.save_pretrained): enc. stripped,
+            # mlm. -> cls. -- a pretraining-layout dict (enc.* keys) is loaded as it is
+            from .checkpoint import from_finetune_keys
+            state_dict = from_finetune_keys(state_dict)
         m = cls(config, args, **kw)
         m.load_state_dict(state_dict, strict=False)
         return m

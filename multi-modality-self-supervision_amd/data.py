@@ -226,3 +226,50 @@ def label_index(txt_labels: torch.Tensor):
     flat = txt_labels.reshape(-1)
     rows = torch.nonzero(flat != -100).view(-1)
     return rows.to(torch.int32), flat[rows].to(torch.int32)
+
+
+_S2S_FAMILY = {"s2s": "s2s", "bi": "1d", "bar": "bar"}
+
+
+def seq2seq_finetune_batch(ids, lengths, n_regions: int, max_len: int, max_pred: int = 10, mask_prob: float = 0.15, mode: str = "s2s",
+                           generator: torch.Generator = None) -> dict:
+    """Host-side batch of the report fine-tuning task as Preprocess4Seq2seq lays it out (Downstream_task/report_generation_and_vqa/sc/
+    data_loader.py:340-419): the inputs of CXRBertForReportFinetune.forward except the image.
+      ids int64 [B, >= max(lengths)] raw text token ids, valid for t < lengths[b]; max_len = the full sequence length
+      [CLS] + n_regions + [SEP] + text, so the text part holds T = max_len - n_regions - 2 ids including its final [SEP].
+      n_pred = min(max_pred, max(1, int(round(len * mask_prob)))) (Python's round); candidates are all text positions including the
+      last [SEP]; with probability 1/2 the last [SEP] takes the final slot (so it can be listed twice); masked positions hold [MASK];
+      the lists are padded with position 0, label 0, weight 0.  mode "s2s" / "bi" / "bar": data_loader.py:395-412 -> the s2s, 1-D and
+      BAR mask families (a MaskDesc).  Seeded by `generator` alone; no claim of bit-equality with random.shuffle."""
+    if mode not in _S2S_FAMILY:
+        raise ValueError(f"mode {mode!r}: one of {sorted(_S2S_FAMILY)}")
+    ids = torch.as_tensor(ids).detach().cpu().to(torch.int64)
+    lengths = torch.as_tensor(lengths).detach().cpu().to(torch.int64).view(-1)
+    B, N = int(lengths.numel()), int(n_regions)
+    T = int(max_len) - N - 2
+    if T < 2 or int(lengths.min()) < 1 or int(lengths.max()) > T - 1 or ids.shape[0] != B or ids.shape[1] < int(lengths.max()):
+        raise ValueError(f"text lengths must lie in [1, {T - 1}] (max_len {max_len} = [CLS] + {N} regions + [SEP] + text + [SEP])")
+    gen = generator if generator is not None else torch.Generator().manual_seed(torch.initial_seed())
+    txt = torch.zeros((B, T), dtype=torch.int64)
+    segment = torch.zeros((B, T), dtype=torch.int64)
+    pos = torch.zeros((B, max_pred), dtype=torch.int64)
+    lab = torch.zeros((B, max_pred), dtype=torch.int64)
+    w = torch.zeros((B, max_pred), dtype=torch.float32)
+    for b in range(B):
+        n = int(lengths[b])
+        txt[b, :n] = ids[b, :n]
+        txt[b, n] = SEP
+        segment[b, :n + 1] = 1
+        n_pred = min(max_pred, max(1, int(round(n * mask_prob))))
+        cand = torch.randperm(n + 1, generator=gen)                   # text indices 0 .. n (n: the last [SEP])
+        if float(torch.rand(1, generator=gen)) > 0.5:
+            chosen = cand[:n_pred - 1].tolist() + [n]
+        else:
+            chosen = cand[:n_pred].tolist()
+        for j, t in enumerate(chosen):
+            pos[b, j], lab[b, j], w[b, j] = N + 2 + t, ids[b, t] if t < n else SEP, 1.0
+        txt[b, chosen] = MASK
+    n_ids = lengths + 1
+    return dict(cls_tok=torch.full((B, 1), CLS, dtype=torch.int64), input_txt=txt, segment=segment,
+                sep_tok=torch.full((B, 1), SEP, dtype=torch.int64), attn_mask=MaskDesc.make(_S2S_FAMILY[mode], N, T - 1, n_ids),
+                masked_pos=pos, masked_lm_labels=lab, masked_weights=w, n_ids=n_ids)

@@ -651,3 +651,77 @@ def bce_multilabel(logits, C, *, R=None, ld=None, target=None, pos_weight=None, 
                                   L.dt_of(dgrad) if dgrad is not None else 0, ldd, L.ptr(grad_scale_dev), float(grad_scale),
                                   L.ptr(loss_scale_dev), L.ptr(probs), L.ptr(counters), L.stream_ptr())
     L.check(rc, f"mv_bce_multilabel(R={R},C={C})")
+
+
+# ---------------------------------------------------------------------------------------------- report fine-tuning (csrc/mv_lmloss.hip)
+def _lm_check(logits, row_ptr, labels, U, V, ld):
+    if logits.dtype != torch.float32:
+        raise TypeError("lm_loss: f32 logits")
+    if row_ptr.dtype != torch.int32 or labels.dtype != torch.int32 or not row_ptr.is_contiguous() or not labels.is_contiguous():
+        raise TypeError("lm_loss: contiguous int32 row_ptr and labels")
+    if row_ptr.numel() != U + 1 or logits.numel() < (U - 1) * ld + V:
+        raise ValueError("lm_loss: row_ptr holds U + 1 offsets and the logits U rows")
+
+
+def lm_loss_fwd(logits, row_ptr, labels, label_smoothing, *, U=None, V=None, ld=None, entry_loss=None, entry_hit=None, row_stat=None):
+    """Per-entry loss of the smoothed masked-LM objective over the CSR entries of the distinct rows (see mv_lm_loss_fwd):
+    -> (entry_loss f32 [n], entry_hit int32 [n], row_stat f32 [U, 2])."""
+    L.require_cuda(logits, row_ptr, labels, entry_loss, entry_hit, row_stat)
+    U = U if U is not None else logits.shape[0]
+    V = V if V is not None else logits.shape[-1]
+    ld = ld if ld is not None else logits.stride(0)
+    n = int(labels.numel())
+    _lm_check(logits, row_ptr, labels, U, V, ld)
+    dev = logits.device
+    entry_loss = entry_loss if entry_loss is not None else torch.empty(n, dtype=torch.float32, device=dev)
+    entry_hit = entry_hit if entry_hit is not None else torch.empty(n, dtype=torch.int32, device=dev)
+    row_stat = row_stat if row_stat is not None else torch.empty((U, 2), dtype=torch.float32, device=dev)
+    if entry_loss.dtype != torch.float32 or entry_hit.dtype != torch.int32 or row_stat.dtype != torch.float32 \
+            or entry_loss.numel() < n or entry_hit.numel() < n or row_stat.numel() < 2 * U:
+        raise TypeError("lm_loss_fwd: entry_loss f32 [n], entry_hit int32 [n], row_stat f32 [U, 2]")
+    rc = _lib().mv_lm_loss_fwd(L.ptr(logits), ld, U, V, L.ptr(row_ptr), L.ptr(labels), n, float(label_smoothing), L.ptr(entry_loss),
+                               L.ptr(entry_hit), L.ptr(row_stat), L.stream_ptr())
+    L.check(rc, f"mv_lm_loss_fwd(U={U},V={V},n={n})")
+    return entry_loss, entry_hit, row_stat
+
+
+def lm_loss_select(entry_loss, weights, sample, entry_hit, B, k):
+    """Drop-worst selection and normalisation (see mv_lm_loss_select): -> (keep int32 [B], stats f32 [4], inv_denom f32 [1])."""
+    L.require_cuda(entry_loss, weights, sample, entry_hit)
+    n = int(weights.numel())
+    if entry_loss.dtype != torch.float32 or weights.dtype != torch.float32 or sample.dtype != torch.int32 \
+            or (entry_hit is not None and entry_hit.dtype != torch.int32):
+        raise TypeError("lm_loss_select: f32 losses and weights, int32 sample indices and hits")
+    if entry_loss.numel() < n or sample.numel() != n or (entry_hit is not None and entry_hit.numel() < n):
+        raise ValueError("lm_loss_select: one loss, weight, sample index and hit per entry")
+    dev = weights.device
+    keep = torch.empty(B, dtype=torch.int32, device=dev)
+    stats = torch.empty(4, dtype=torch.float32, device=dev)
+    inv = torch.empty(1, dtype=torch.float32, device=dev)
+    rc = _lib().mv_lm_loss_select(L.ptr(entry_loss), L.ptr(weights), L.ptr(sample), L.ptr(entry_hit), n, int(B), int(k), L.ptr(keep),
+                                  L.ptr(stats), L.ptr(inv), L.stream_ptr())
+    L.check(rc, f"mv_lm_loss_select(B={B},k={k},n={n})")
+    return keep, stats, inv
+
+
+def lm_loss_bwd(logits, row_ptr, labels, weights, sample, label_smoothing, row_stat, keep, inv_denom, grad_dev, dlogits, *, U=None,
+                V=None, ld=None, ldd=None, loss_scale_dev=None):
+    """dlogits [U, ldd] (f32 / bf16 / f16; columns V..ldd-1 zero) of the objective (see mv_lm_loss_bwd)."""
+    L.require_cuda(logits, row_ptr, labels, weights, sample, row_stat, keep, inv_denom, grad_dev, dlogits, loss_scale_dev)
+    U = U if U is not None else logits.shape[0]
+    V = V if V is not None else logits.shape[-1]
+    ld = ld if ld is not None else logits.stride(0)
+    ldd = ldd if ldd is not None else dlogits.stride(0)
+    n = int(labels.numel())
+    _lm_check(logits, row_ptr, labels, U, V, ld)
+    if weights.dtype != torch.float32 or sample.dtype != torch.int32 or keep.dtype != torch.int32 or weights.numel() != n or sample.numel() != n:
+        raise TypeError("lm_loss_bwd: f32 weights [n], int32 sample [n], int32 keep [B]")
+    if any(t.dtype != torch.float32 for t in (row_stat, inv_denom, grad_dev)) or row_stat.numel() < 2 * U:
+        raise TypeError("lm_loss_bwd: f32 row_stat [U, 2], inv_denom [1], grad_dev [1]")
+    if dlogits.numel() < (U - 1) * ldd + max(ldd, V) and U > 0:
+        raise ValueError("lm_loss_bwd: dlogits holds U rows of ldd columns")
+    rc = _lib().mv_lm_loss_bwd(L.ptr(logits), ld, U, V, L.ptr(row_ptr), L.ptr(labels), L.ptr(weights), L.ptr(sample), n,
+                               float(label_smoothing), L.ptr(row_stat), L.ptr(keep), L.ptr(inv_denom), L.ptr(grad_dev),
+                               L.ptr(loss_scale_dev), L.ptr(dlogits), L.dt_of(dlogits), ldd, L.stream_ptr())
+    L.check(rc, f"mv_lm_loss_bwd(U={U},V={V},n={n})")
+    return dlogits

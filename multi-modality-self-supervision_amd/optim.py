@@ -179,8 +179,9 @@ class BertAdam(torch.optim.Optimizer):
 
     `params`: model.parameters() or the reference's grouped list; groups may differ in `weight_decay` only, and the positive values
     must agree (the kernel takes one value and a per-tensor flag).  Ownership as AdamW: all Parameters of ONE CXRBERT, optionally plus
-    the whole head of its CXRBertForVQA / CXRBertForClassification.  Tensors the task's graph does not reach (named by the task module:
-    MLM / ITM heads, the pooler under VQA) are `grad is None` in the reference and stay bit-unchanged here.  Differences, documented:
+    the whole head of its CXRBertForVQA / CXRBertForClassification, or the CXRBERT of a CXRBertForReportFinetune (no head Parameters).
+    Tensors the task's graph does not reach (named by the task module: MLM / ITM heads, the pooler under VQA; the ITM head and the
+    pooler under report fine-tuning) are `grad is None` in the reference and stay bit-unchanged here.  Differences, documented:
     one step counter for all tensors (the reference keeps one per tensor; they only diverge for a tensor that has a gradient in some
     steps and none in others, which is refused here), and `.grad` is left unclipped."""
 
@@ -238,6 +239,10 @@ class BertAdam(torch.optim.Optimizer):
         if len({float(g["weight_decay"]) for g in self.param_groups if g["weight_decay"] > 0.0}) > 1:
             raise ValueError("parameter groups with different positive weight_decay values: the kernel takes one value and a per-tensor flag")
         self._model, self._task, self._t = model, (task if n_head else None), 0
+        # a task module without head Parameters (CXRBertForReportFinetune) registers itself on its encoder: it contributes the names of
+        # the tensors its graph does not reach, nothing else.  A bare CXRBERT carries no such reference
+        ref = getattr(model, "_headless_task", None)
+        self._headless = ref() if (ref is not None and self._task is None) else None
         self._tab = self._htab = self._ent = None
         self._decay_key = None
 
@@ -262,7 +267,7 @@ class BertAdam(torch.optim.Optimizer):
         model = self._model
         decay = self._decay_ids()
         # (the task module is known through its head's Parameters: an encoder passed alone is updated whole)
-        off_graph = tuple(getattr(self._task, "_unreached", ()))
+        off_graph = tuple(getattr(self._task if self._task is not None else self._headless, "_unreached", ()))
         out = []
         for name, par in zip(model._param_names, model._plist):
             off, shape = model.engine.layout[name]
