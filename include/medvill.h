@@ -557,6 +557,46 @@ int mv_lm_loss_bwd(const float* logits, int ld, int U, int V, const int32_t* row
                    const float* inv_denom, const float* grad_dev, const float* loss_scale_dev, void* dlogits, int d_dtype, int ldd,
                    void* stream);
 
+/* ---- image-report retrieval from device-resident banks (csrc/mv_retrieval.hip) ---------------------------------------------
+ * The reference's Downstream_task/Retrieval/full_dset_retrieval.py: the training sampler of CXR_Retrieval_Dataset.__getitem__
+ * (:108-143), the pair batches of data_processing (:172-215) and the ranking metrics of compute_ranks / compute_recall_precision /
+ * compute_mrr (:250-324).  Additive entry points.
+ *
+ * mv_pair_draws: the sampler's random words.  draws uint32 [B, D, 2] (D <= 300): entry (i, t) = the two words {w0, w1} of attempt t
+ *     of sample i, from the counter-based hash keyed by (key, step) at counters 2c, 2c + 1 with c = 300 i + t.
+ * mv_pair_negatives: for positive i with dataset index d = idx[i] (int32 [B], clamped to [0, n)) in a dataset of n >= 2 items:
+ *     r = (uint64(w0) * (n - 1)) >> 32, other = r + (r >= d); the negative is (image other, text d) when w1's top bit is set, else
+ *     (image d, text other).  class_id int32 [n] (nullable; the reference's label_conditioned mode): attempts t = 0, 1, ... are drawn
+ *     while class_id[other] == class_id[d], at most 300, and the last one is kept.  draws (nullable) uint32 [B, n_draws, 2] replaces
+ *     the hash (attempt t reads entry t; at most min(n_draws, 300) attempts), else the words are those of mv_pair_draws.
+ *     pairs int32 [2B, 2] = (image item, text item): the B positives (d, d), then the B negatives; labels int32 [2B] = ones, then
+ *     zeros -- the order of the reference's torch.cat (:360-366).
+ * mv_pair_assemble: one launch per batch.  Banks: txt_ids int64 [T_items, S+1] (each row tokens + [SEP] + [PAD]...), txt_len int32
+ *     [T_items] (counting the [SEP]), img_feats [I_items, N, F] (dtype), img_pos int64 [I_items, N] (nullable, with pos_out);
+ *     pairs int32 [R, 2] (an index outside its bank is clamped into it).  Writes input_txt int64 [R, S+1], segment int64 [R, S+1]
+ *     (all ones, :203), n_ids int32 [R], desc int32 [R, 3] = {4 (1-D family), N+2, N+2+len}, feats [R, N, F] (dtype), pos_out
+ *     int64 [R, N].
+ * mv_rank_groups: logits f32 [G*C, 2], labels int32 [G*C] (1 = aligned), ks = HOST array of nk <= 8 positive cut-offs.
+ *     p f32 [G*C] = softmax(logits)[:, 1] in f32; everything else ranks the WRITTEN p.  pos int32 [G*C] = candidates of the same
+ *     group ahead of this one: descending p, exact ties by the HIGHER candidate index first, NaN after every number -- what
+ *     reversing a stable ascending sort gives (np.argsort(sim)[::-1]; numpy's default sort is stable for short arrays only, so the
+ *     reference's order among exact ties is otherwise unspecified, and numpy would put NaN first).  rank int32 [G] = the least pos
+ *     among aligned candidates, C when none is aligned.  counters uint64 [28], ACCUMULATED (zero them first): [0] groups,
+ *     [1] groups without an aligned candidate, [2] sum of fx(1 / (rank + 1)), [3] unused, [4+q] sum of [rank < k_q],
+ *     [12+q] sum over groups with an aligned candidate of fx(aligned in the top k_q / aligned in the group), [20+q] sum of aligned in
+ *     the top k_q (precision@k_q = that / k_q; k_q > C takes the whole group); fx(x) = rint(x * 2^32) of the f64 quotient, so the
+ *     sums are integers and do not depend on the order in which groups finish.  One block per group, any C >= 1.
+ * Null pointers, non-positive sizes, n < 2, C < 1, nk > 8, a cut-off <= 0: MV_E_ARG; unknown dtype: MV_E_DTYPE; D > 300 or sizes past
+ * the 32-bit counters: MV_E_SHAPE.  */
+int mv_pair_draws(unsigned long long key, unsigned long long step, int B, int D, uint32_t* draws, void* stream);
+int mv_pair_negatives(const int32_t* idx, int B, int n, const int32_t* class_id, unsigned long long key, unsigned long long step,
+                      const uint32_t* draws, int n_draws, int32_t* pairs, int32_t* labels, void* stream);
+int mv_pair_assemble(const int64_t* txt_ids, const int32_t* txt_len, int T_items, const void* img_feats, int dtype, int I_items,
+                     const int64_t* img_pos, const int32_t* pairs, int R, int N, int S, int F, int64_t* input_txt, int64_t* segment,
+                     int32_t* n_ids, int32_t* desc, void* feats, int64_t* pos_out, void* stream);
+int mv_rank_groups(const float* logits, const int32_t* labels, int G, int C, const int32_t* ks, int nk, float* p, int32_t* pos,
+                   int32_t* rank, unsigned long long* counters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

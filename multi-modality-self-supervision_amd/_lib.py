@@ -91,6 +91,11 @@ PROTOTYPES = {
     "mv_lm_loss_fwd": [vp, i32, i32, i32, vp, vp, i32, f64, vp, vp, vp, vp],
     "mv_lm_loss_select": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "mv_lm_loss_bwd": [vp, i32, i32, i32, vp, vp, vp, vp, i32, f64, vp, vp, vp, vp, vp, vp, i32, i32, vp],
+    # retrieval from device-resident banks (csrc/mv_retrieval.hip)
+    "mv_pair_draws": [u64, u64, i32, i32, vp, vp],
+    "mv_pair_negatives": [vp, i32, i32, vp, u64, u64, vp, i32, vp, vp, vp],
+    "mv_pair_assemble": [vp, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+    "mv_rank_groups": [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp],
 }
 # include/medvill_debug.h: exported by libmedvill_hip_dbg.so only
 DEBUG_PROTOTYPES = {"mv_debug_set_knob": [i32, i32], "mv_debug_get_knob": [i32]}

@@ -273,3 +273,128 @@ def seq2seq_finetune_batch(ids, lengths, n_regions: int, max_len: int, max_pred:
     return dict(cls_tok=torch.full((B, 1), CLS, dtype=torch.int64), input_txt=txt, segment=segment,
                 sep_tok=torch.full((B, 1), SEP, dtype=torch.int64), attn_mask=MaskDesc.make(_S2S_FAMILY[mode], N, T - 1, n_ids),
                 masked_pos=pos, masked_lm_labels=lab, masked_weights=w, n_ids=n_ids)
+
+
+# ---------------------------------------------------------------------------------------------------- retrieval banks
+def check_pairs(pairs, n_images: int, n_texts: int) -> torch.Tensor:
+    """Host-side check of a pair list given on the host: -> int32 [R, 2] (image item, text item), every index inside its bank."""
+    p = torch.as_tensor(pairs)
+    if p.dim() != 2 or p.shape[1] != 2 or p.shape[0] == 0 or p.dtype.is_floating_point or p.dtype == torch.bool:
+        raise ValueError("pairs must be a non-empty integer [R, 2] list of (image item, text item)")
+    p = p.to(torch.int64)
+    if int(p[:, 0].min()) < 0 or int(p[:, 0].max()) >= n_images:
+        raise IndexError(f"pairs name an image outside the bank of {n_images}")
+    if int(p[:, 1].min()) < 0 or int(p[:, 1].max()) >= n_texts:
+        raise IndexError(f"pairs name a text outside the bank of {n_texts}")
+    return p.to(torch.int32).contiguous()
+
+
+class RetrievalBank:
+    """The two sides of a retrieval data set, resident on the device (Downstream_task/Retrieval/full_dset_retrieval.py builds every pair
+    on the host, and pushes an image through the region encoder once per pair it appears in):
+      add_texts(ids, lengths)   ids int64 [n, S+1], each row tokens + [SEP] + [PAD]... as data_processing (:183-198) lays it out;
+                                lengths [n] count the [SEP]
+      add_images(input_img)     whatever CXRBERT.forward accepts as input_img -- (region features [n, N, F], positions [n, N]) or pixels for
+                                the model's region encoder -- run ONCE per distinct image; the features are stored in the engine's input
+                                encoding
+      assemble(pairs)           (image item, text item) index pairs -> the arguments of CXRBertForRetrieval.forward, with `attn_mask` a
+                                MaskDesc of the 1-D family (one mv_pair_assemble launch).  Pairs given on the host are checked against the
+                                banks there and the descriptors' host copy is built from the lengths' host copy (no read-back); pairs that
+                                live on the device are clamped into the banks by the kernel.
+    `model`: a CXRBertForRetrieval / CXRBERT (its engine gives device and encoding); None with device= / feat_dtype= for host-only use."""
+
+    def __init__(self, model=None, device=None, feat_dtype=None, class_id=None):
+        bert = getattr(model, "bert", model)
+        self.bert = bert
+        if bert is not None:
+            eng = bert.engine
+            device = eng.device if device is None else device
+            feat_dtype = (eng.adt if eng.is16 else torch.float32) if feat_dtype is None else feat_dtype
+        self.device = torch.device(device if device is not None else "cpu")
+        self.feat_dtype = feat_dtype if feat_dtype is not None else torch.float32
+        self.txt_ids = self.txt_len = self.img_feats = self.img_pos = None
+        self._len_host = None
+        self.class_id = None
+        self._tok = {}
+        if class_id is not None:
+            self.set_classes(class_id)
+
+    @property
+    def n_texts(self):
+        return 0 if self.txt_ids is None else int(self.txt_ids.shape[0])
+
+    @property
+    def n_images(self):
+        return 0 if self.img_feats is None else int(self.img_feats.shape[0])
+
+    def add_texts(self, ids, lengths):
+        ids = torch.as_tensor(ids).to(torch.int64)
+        lens = torch.as_tensor(lengths).to(torch.int32).reshape(-1)
+        if ids.dim() != 2 or ids.shape[1] < 2 or lens.numel() != ids.shape[0]:
+            raise ValueError("add_texts: ids int64 [n, S+1] and one length per row")
+        host = lens.cpu()               # (one copy when the bank is filled: batches never read lengths back)
+        if int(host.min()) < 1 or int(host.max()) > ids.shape[1]:
+            raise ValueError(f"add_texts: lengths count the [SEP], so they lie in [1, {ids.shape[1]}]")
+        if self.txt_ids is not None and self.txt_ids.shape[1] != ids.shape[1]:
+            raise ValueError("add_texts: every row of the bank has the same S+1 columns")
+        ids, lens = ids.to(self.device).contiguous(), lens.to(self.device).contiguous()
+        self.txt_ids = ids if self.txt_ids is None else torch.cat([self.txt_ids, ids])
+        self.txt_len = lens if self.txt_len is None else torch.cat([self.txt_len, lens])
+        self._len_host = host if self._len_host is None else torch.cat([self._len_host, host])
+        return self
+
+    @torch.no_grad()
+    def add_images(self, input_img):
+        if self.bert is not None:
+            feats, pos = self.bert._regions(input_img)
+        else:
+            feats, pos = input_img
+        if feats.dim() != 3 or tuple(pos.shape) != tuple(feats.shape[:2]):
+            raise ValueError("add_images: region features [n, N, F] and positions [n, N]")
+        if self.img_feats is not None and tuple(self.img_feats.shape[1:]) != tuple(feats.shape[1:]):
+            raise ValueError("add_images: every image of the bank has the same [N, F] regions")
+        feats = feats.detach().to(self.device, self.feat_dtype).contiguous()
+        pos = pos.detach().to(self.device, torch.int64).contiguous()
+        self.img_feats = feats if self.img_feats is None else torch.cat([self.img_feats, feats])
+        self.img_pos = pos if self.img_pos is None else torch.cat([self.img_pos, pos])
+        return self
+
+    def set_classes(self, class_id):
+        """int [n]: the class of item i for the sampler's label_conditioned mode (None: plain sampling)."""
+        self.class_id = None if class_id is None else torch.as_tensor(class_id).to(torch.int32).reshape(-1).to(self.device).contiguous()
+        return self
+
+    def _tokens(self, R):
+        t = self._tok.get(R)
+        if t is None:
+            t = self._tok[R] = (torch.full((R, 1), CLS, dtype=torch.int64, device=self.device),
+                                torch.full((R, 1), SEP, dtype=torch.int64, device=self.device))
+        return t
+
+    def host_descriptors(self, pairs_host):
+        """int32 [R, 3] = {FAMILY_ID['1d'], N+2, N+2+len}: what mv_pair_assemble writes, from the host copy of the lengths."""
+        N = int(self.img_feats.shape[1])
+        ln = self._len_host.index_select(0, pairs_host[:, 1].to(torch.int64))
+        d = torch.empty((pairs_host.shape[0], 3), dtype=torch.int32)
+        d[:, 0], d[:, 1], d[:, 2] = FAMILY_ID["1d"], N + 2, N + 2 + ln
+        return d
+
+    def assemble(self, pairs):
+        """-> (cls_tok, input_txt, attn_mask, segment, input_img, sep_tok), attn_mask a MaskDesc, input_img = (features, positions)."""
+        from . import hip_ops as ops
+        if self.txt_ids is None or self.img_feats is None:
+            raise RuntimeError("RetrievalBank.assemble: fill both banks first (add_texts, add_images)")
+        host = None
+        if torch.is_tensor(pairs) and pairs.device.type != "cpu":
+            if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
+                raise TypeError("pairs on the device: int32 [R, 2]")
+            dev_pairs = pairs.contiguous()
+        else:
+            hp = check_pairs(pairs, self.n_images, self.n_texts)
+            host = self.host_descriptors(hp)
+            dev_pairs = hp.to(self.device)
+        out = ops.pair_assemble(self.txt_ids, self.txt_len, self.img_feats, self.img_pos, dev_pairs)
+        R, N, T = int(dev_pairs.shape[0]), int(self.img_feats.shape[1]), int(self.txt_ids.shape[1])
+        cls_tok, sep_tok = self._tokens(R)
+        desc = MaskDesc(out["desc"], T + N + 2, host=host)
+        return cls_tok, out["input_txt"], desc, out["segment"], (out["feats"], out["pos"]), sep_tok

@@ -725,3 +725,99 @@ def lm_loss_bwd(logits, row_ptr, labels, weights, sample, label_smoothing, row_s
                                L.ptr(loss_scale_dev), L.ptr(dlogits), L.dt_of(dlogits), ldd, L.stream_ptr())
     L.check(rc, f"mv_lm_loss_bwd(U={U},V={V},n={n})")
     return dlogits
+
+
+# ---------------------------------------------------------------------------------------------------- retrieval (csrc/mv_retrieval.hip)
+RANK_NCOUNT = 28          # mv_rank_groups' counters: include/medvill.h
+PAIR_MAX_DRAWS = 300
+
+
+def _words_to_i32(w):
+    """32-bit words given as integers in [0, 2^32) (any integer dtype) -> their bit patterns in an int32 tensor."""
+    w = torch.as_tensor(w).to(torch.int64)
+    return (((w + 2 ** 31) % 2 ** 32) - 2 ** 31).to(torch.int32)
+
+
+def _i32_to_words(w):
+    return w.to(torch.int64) & 0xFFFFFFFF
+
+
+def pair_draws(key, step, B, D, device):
+    """int64 [B, D, 2] holding the 32-bit words {w0, w1} of attempt t of sample i (see mv_pair_draws)."""
+    out = torch.empty((B, D, 2), dtype=torch.int32, device=device)
+    L.require_cuda(out)
+    rc = _lib().mv_pair_draws(int(key) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(B), int(D), L.ptr(out), L.stream_ptr())
+    L.check(rc, f"mv_pair_draws(B={B},D={D})")
+    return _i32_to_words(out)
+
+
+def pair_negatives(idx, n, key=0, step=0, class_id=None, draws=None):
+    """The retrieval training sampler (see mv_pair_negatives): idx int32 [B] on the device -> (pairs int32 [2B, 2], labels int32 [2B]).
+    draws: integers in [0, 2^32), [B, D, 2] (or [B, 2] for D = 1), replacing the hash-generated words."""
+    L.require_cuda(idx, class_id)
+    if idx.dtype != torch.int32 or idx.dim() != 1:
+        raise TypeError("pair_negatives: idx int32 [B]")
+    if class_id is not None and (class_id.dtype != torch.int32 or tuple(class_id.shape) != (int(n),)):
+        raise TypeError("pair_negatives: class_id int32 [n]")
+    B, dev = int(idx.numel()), idx.device
+    d32, D = None, 0
+    if draws is not None:
+        d32 = _words_to_i32(draws).to(dev).reshape(B, -1, 2).contiguous()
+        D = int(d32.shape[1])
+    pairs = torch.empty((2 * B, 2), dtype=torch.int32, device=dev)
+    labels = torch.empty((2 * B,), dtype=torch.int32, device=dev)
+    rc = _lib().mv_pair_negatives(L.ptr(idx.contiguous()), B, int(n), L.ptr(class_id), int(key) & 0xFFFFFFFFFFFFFFFF,
+                                  int(step) & 0xFFFFFFFFFFFFFFFF, L.ptr(d32), D, L.ptr(pairs), L.ptr(labels), L.stream_ptr())
+    L.check(rc, f"mv_pair_negatives(B={B},n={n})")
+    return pairs, labels
+
+
+def pair_assemble(txt_ids, txt_len, img_feats, img_pos, pairs):
+    """Pair batches from the banks (see mv_pair_assemble): -> dict(input_txt, segment, n_ids, desc, feats, pos)."""
+    L.require_cuda(txt_ids, txt_len, img_feats, img_pos, pairs)
+    if txt_ids.dtype != torch.int64 or txt_len.dtype != torch.int32 or pairs.dtype != torch.int32 or (img_pos is not None and img_pos.dtype != torch.int64):
+        raise TypeError("pair_assemble: txt_ids int64, txt_len int32, pairs int32, img_pos int64")
+    if txt_ids.dim() != 2 or img_feats.dim() != 3 or pairs.dim() != 2 or pairs.shape[1] != 2 or tuple(txt_len.shape) != (txt_ids.shape[0],):
+        raise ValueError("pair_assemble: txt_ids [T_items, S+1], txt_len [T_items], img_feats [I_items, N, F], pairs [R, 2]")
+    if not (txt_ids.is_contiguous() and img_feats.is_contiguous() and pairs.is_contiguous() and txt_len.is_contiguous()):
+        raise ValueError("pair_assemble: contiguous tensors")
+    Ti, T = txt_ids.shape
+    Ii, N, F = img_feats.shape
+    if img_pos is not None and (tuple(img_pos.shape) != (Ii, N) or not img_pos.is_contiguous()):
+        raise ValueError("pair_assemble: img_pos [I_items, N]")
+    R, dev = int(pairs.shape[0]), txt_ids.device
+    out = dict(input_txt=torch.empty((R, T), dtype=torch.int64, device=dev), segment=torch.empty((R, T), dtype=torch.int64, device=dev),
+               n_ids=torch.empty((R,), dtype=torch.int32, device=dev), desc=torch.empty((R, 3), dtype=torch.int32, device=dev),
+               feats=torch.empty((R, N, F), dtype=img_feats.dtype, device=dev),
+               pos=None if img_pos is None else torch.empty((R, N), dtype=torch.int64, device=dev))
+    rc = _lib().mv_pair_assemble(L.ptr(txt_ids), L.ptr(txt_len), int(Ti), L.ptr(img_feats), L.dt_of(img_feats), int(Ii), L.ptr(img_pos),
+                                 L.ptr(pairs), R, int(N), int(T) - 1, int(F), L.ptr(out["input_txt"]), L.ptr(out["segment"]),
+                                 L.ptr(out["n_ids"]), L.ptr(out["desc"]), L.ptr(out["feats"]), L.ptr(out["pos"]), L.stream_ptr())
+    L.check(rc, f"mv_pair_assemble(R={R},N={N},S={T - 1},F={F})")
+    return out
+
+
+def rank_groups(logits, labels, C, ks=(1, 5, 10), counters=None):
+    """Ranking of G groups of C candidates (see mv_rank_groups): -> (p f32 [G*C], pos int32 [G*C], rank int32 [G], counters int64 [28]);
+    `counters` (int64 [28] on the device) is accumulated into when given."""
+    import ctypes
+    L.require_cuda(logits, labels, counters)
+    if logits.dtype != torch.float32 or labels.dtype != torch.int32 or not logits.is_contiguous() or not labels.is_contiguous():
+        raise TypeError("rank_groups: contiguous f32 logits [G*C, 2] and int32 labels [G*C]")
+    n, C = int(labels.numel()), int(C)
+    if C < 1 or n == 0 or n % C != 0 or logits.numel() != 2 * n:
+        raise ValueError(f"rank_groups: {n} candidates do not form groups of {C} (logits [G*C, 2], labels [G*C])")
+    dev = logits.device
+    if counters is None:
+        counters = torch.zeros(RANK_NCOUNT, dtype=torch.int64, device=dev)
+    elif counters.dtype != torch.int64 or counters.numel() != RANK_NCOUNT or not counters.is_contiguous():
+        raise TypeError(f"rank_groups: counters int64 [{RANK_NCOUNT}]")
+    ks = [int(k) for k in ks]
+    karr = (ctypes.c_int * max(len(ks), 1))(*ks)
+    p = torch.empty(n, dtype=torch.float32, device=dev)
+    pos = torch.empty(n, dtype=torch.int32, device=dev)
+    rank = torch.empty(n // C, dtype=torch.int32, device=dev)
+    rc = _lib().mv_rank_groups(L.ptr(logits), L.ptr(labels), n // C, C, ctypes.cast(karr, ctypes.c_void_p), len(ks), L.ptr(p), L.ptr(pos),
+                               L.ptr(rank), L.ptr(counters), L.stream_ptr())
+    L.check(rc, f"mv_rank_groups(G={n // C},C={C},ks={ks})")
+    return p, pos, rank, counters
