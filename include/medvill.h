@@ -131,6 +131,41 @@ int mv_gemm(int dtype, int ta, int tb, int M, int N, int K,
 size_t mv_gemm_workspace_bytes(int dtype, int ta, int tb, int M, int N, int K);
 size_t mv_workspace_bytes(int hidden, int intermediate, int vocab, int img_hidden, int max_rows, int max_label_rows, int max_regions);
 
+/* ---- grouped weight gradients ---------------------------------------------------------------
+ * Many independent products C_i[No_i, Ko_i] (+)= [*alpha_dev] * A_i[rows_i, No_i]^T . B_i[rows_i, Ko_i]  (the dW = dy^T.x form of
+ * mv_gemm: 16-bit A and B of one encoding, f32 C) in ONE persistent launch over full contractions: a single product of a layer has
+ * too few 256 x 256 tiles for the chip and needs split-K slabs, the products of all layers together do not.  Only the tiles that do
+ * not fill a last round of blocks are cut along K (slabs in `ws`, folded by one reduction launch).
+ *   mv_gemm_grouped_table_bytes      size of the table for `count` problems (0 for count <= 0).
+ *   mv_gemm_grouped_fill             validates `problems` (host array) and writes the table into HOST memory `table_host`; n_blocks
+ *                                    = blocks the launch will use (0: one per CU of the current device).  Pure host arithmetic.
+ *                                    The caller keeps a copy of the table in device memory and refreshes it only when a problem
+ *                                    changed: a launch copies nothing from the host.
+ *   mv_gemm_grouped_workspace_bytes  bytes of `ws` the launch of this (host) table needs (0: nothing is split).
+ *   mv_gemm_grouped_decode           launch unit -> out[7] = {problem, m0, n0, kbeg, kend, slice (-1: unsplit), flat tile}: the
+ *                                    map the kernel itself uses, for hosts and tests that want to inspect a plan.
+ *   mv_gemm_grouped_tn               the launch.  table_host: what mv_gemm_grouped_fill wrote (re-validated here; it decides the
+ *                                    grid); table_dev: its device copy, which is all the kernels read.  The library cannot read
+ *                                    device memory on the host, so table_dev is NOT checked: it must hold, when the launch runs
+ *                                    on `stream`, the very bytes of table_host (all mv_gemm_grouped_table_bytes(count) of them).
+ *                                    A stale or foreign device copy makes the kernels read and write through its pointers.
+ *                                    accumulate / alpha_dev as in mv_gemm.
+ * Per problem: A, B, C non-null, sizes positive (MV_E_ARG); A and B 16-byte aligned, C 4-byte aligned, lda and ldb multiples of
+ * 8, lda >= No, ldb >= Ko, ldc >= Ko, every operand below 2 GiB, at most 256 problems (MV_E_SHAPE); dtype MV_BF16 or MV_F16
+ * (MV_E_DTYPE); a null or foreign table, count <= 0 (MV_E_ARG); a table buffer or `ws` that is too small (MV_E_WORKSPACE).  A call
+ * that fails launches nothing.  */
+typedef struct mv_group_problem {
+  const void* A; const void* B; void* C;
+  int lda, ldb, ldc;
+  int No, Ko, rows;
+} mv_group_problem;
+size_t mv_gemm_grouped_table_bytes(int count);
+int mv_gemm_grouped_fill(int dtype, int count, const mv_group_problem* problems, int n_blocks, void* table_host, size_t table_bytes);
+size_t mv_gemm_grouped_workspace_bytes(const void* table_host);
+int mv_gemm_grouped_decode(const void* table_host, int unit, int* out);
+int mv_gemm_grouped_tn(int dtype, int count, const void* table_host, const void* table_dev, float* ws, size_t ws_bytes,
+                       int accumulate, const float* alpha_dev, void* stream);
+
 /* ---- attention masks ----------------------------------------------------------------------
  * Replaces CXRBertEncoder.get_extended_attn_mask (cxrbert_origin.py:75-85): instead of an
  * fp16 additive [B,1,L,L] tensor the int64 0/1 mask the Dataset built

@@ -38,6 +38,11 @@ PROTOTYPES = {
                 i32, vp, sz, i32, f32, u64, vp, vp, vp],
     "mv_gemm_workspace_bytes": [i32, i32, i32, i32, i32, i32],
     "mv_workspace_bytes": [i32, i32, i32, i32, i32, i32, i32],
+    "mv_gemm_grouped_table_bytes": [i32],
+    "mv_gemm_grouped_fill": [i32, i32, vp, i32, vp, sz],
+    "mv_gemm_grouped_workspace_bytes": [vp],
+    "mv_gemm_grouped_decode": [vp, i32, C.POINTER(C.c_int)],
+    "mv_gemm_grouped_tn": [i32, i32, vp, vp, vp, sz, i32, vp, vp],
     "mv_mask_pack": [vp, i32, i32, i32, vp, vp, vp],
     "mv_mask_build": [vp, i32, i32, vp, vp, vp],
     "mv_mask_verify_host": [vp, i32, vp, i32, i32, i32, C.POINTER(C.c_longlong)],
@@ -99,7 +104,8 @@ PROTOTYPES = {
 }
 # include/medvill_debug.h: exported by libmedvill_hip_dbg.so only
 DEBUG_PROTOTYPES = {"mv_debug_set_knob": [i32, i32], "mv_debug_get_knob": [i32]}
-_RESTYPE = {"mv_build_info": C.c_char_p, "mv_gemm_workspace_bytes": C.c_size_t, "mv_workspace_bytes": C.c_size_t}
+_RESTYPE = {"mv_build_info": C.c_char_p, "mv_gemm_workspace_bytes": C.c_size_t, "mv_workspace_bytes": C.c_size_t,
+            "mv_gemm_grouped_table_bytes": C.c_size_t, "mv_gemm_grouped_workspace_bytes": C.c_size_t}
 ABI_VERSION = 6
 
 # knob name -> (id, default): csrc/mv_common.h / include/medvill_debug.h

@@ -17,6 +17,7 @@
 //
 // Reference work replaced: every nn.Linear on the path (see include/medvill.h, mv_gemm).
 #include "mv_gemm_common.h"
+#include "mv_gemm_group.h"
 
 // ------------------------------------------------------------------------------------------
 // MFMA kernel
@@ -611,6 +612,51 @@ extern "C" int mv_gemm(int dtype, int ta, int tb, int M, int N, int K, const voi
     MV_CHECK_LAUNCH();
   }
   return MV_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Grouped weight gradients: many dW = dy^T.x products in one persistent launch over full contractions (include/medvill.h).  The
+// table, the unit map and the tail rule are plain host code in mv_gemm_group.h; this file only validates and launches.
+int mv_launch_ring_tn_grouped(const MvGroupHeader& h, const GroupArgs& ga, bool f16, int n_blk, hipStream_t stream);    // mv_gemm_ring_tn.hip
+
+static int grouped_blocks() {
+  const int n_cu = gemm_n_cu();
+  return (g_mv_persistent_cus > 0 && g_mv_persistent_cus < n_cu) ? g_mv_persistent_cus : n_cu;
+}
+
+extern "C" size_t mv_gemm_grouped_table_bytes(int count) { return mv_group_table_bytes(count); }
+
+extern "C" int mv_gemm_grouped_fill(int dtype, int count, const mv_group_problem* problems, int n_blocks, void* table_host, size_t table_bytes) {
+  if (n_blocks < 0) return MV_E_ARG;
+  return mv_group_fill(dtype, count, problems, n_blocks > 0 ? n_blocks : grouped_blocks(), table_host, table_bytes);
+}
+
+extern "C" size_t mv_gemm_grouped_workspace_bytes(const void* table_host) { return mv_group_workspace_bytes(table_host); }
+
+extern "C" int mv_gemm_grouped_decode(const void* table_host, int unit, int* out) {
+  if (!table_host || !out) return MV_E_ARG;
+  const MvGroupHeader& h = *(const MvGroupHeader*)table_host;
+  if (h.magic != MV_GROUP_MAGIC || unit < 0 || unit >= h.direct + h.tail * h.split) return MV_E_ARG;
+  const MvGroupUnit d = mv_group_decode(h, (const MvGroupEntry*)((const char*)table_host + sizeof(MvGroupHeader)), unit);
+  out[0] = d.problem; out[1] = d.m0; out[2] = d.n0; out[3] = d.kbeg; out[4] = d.kend; out[5] = d.slice; out[6] = d.tile;
+  return MV_OK;
+}
+
+extern "C" int mv_gemm_grouped_tn(int dtype, int count, const void* table_host, const void* table_dev, float* ws, size_t ws_bytes,
+                                  int accumulate, const float* alpha_dev, void* stream_) {
+  if (!table_host || !table_dev || count <= 0) return MV_E_ARG;
+  const int rc = mv_group_check_table(dtype, count, table_host);
+  if (rc != MV_OK) return rc;
+  if (g_mv_impl != 0) return MV_E_DTYPE;                  // MFMA kernels only
+  if (((uintptr_t)table_dev) & 15) return MV_E_SHAPE;
+  const MvGroupHeader& h = *(const MvGroupHeader*)table_host;
+  const size_t need = mv_group_workspace_bytes(table_host);
+  if (need > 0 && (!ws || ws_bytes < need || (((uintptr_t)ws) & 15))) return MV_E_WORKSPACE;
+  GroupArgs ga;
+  ga.table = table_dev; ga.ws = ws; ga.alpha = alpha_dev; ga.accumulate = accumulate;
+  // the plan fixes how the tail is cut for h.n_blocks blocks; any grid computes the same result (a unit's owner is unit mod grid)
+  const int n_blk = h.n_blocks < grouped_blocks() ? h.n_blocks : grouped_blocks();
+  return mv_launch_ring_tn_grouped(h, ga, dtype == MV_F16, n_blk, (hipStream_t)stream_);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // instantiations and their launchers live in mv_gemm_ring_{nt,nn,tn,tnn}.hip, one translation unit per operand layout.
 #pragma once
 #include "mv_gemm_common.h"
+#include "mv_gemm_group.h"
 
 // One ring stage's MFMAs for the layouts with a contraction-major operand (fragments through `ds_read_b64_tr_b16`).  hipcc reads each
 // A fragment right before the MFMAs that consume it (register pressure), so every group of NJ MFMAs starts with a full LDS round
@@ -321,8 +322,130 @@ __global__ __launch_bounds__(128 * WN, 1) void gemm_pring_kernel(GemmArgs p, int
 }
 
 
+// ------------------------------------------------------------------------------------------
+// Grouped form of gemm_pring_kernel<true, true, ...> (dW = dy^T.x): the units of MANY independent products in one persistent
+// launch (mv_gemm_grouped_tn).  The same ring, main loop and epilogue; what changes per unit is where its operands live.  A
+// device-resident table (mv_gemm_group.h) holds one entry per product; a unit is decoded to (problem, tile, K-slice) with the
+// function the host uses, and the problem's pointers, leading dimensions and buffer resources are re-read per unit through the
+// constant address space (wave-uniform scalar loads: they live in SGPRs).  Unsplit units finish in C like an unsplit mv_gemm
+// (alpha, optional accumulate); the K-slices of the tail tiles write 256 x 256 f32 slabs for splitk_reduce_grouped_kernel.
+typedef const __attribute__((address_space(4))) MvGroupEntry* group_tab_t;
+__device__ __forceinline__ MvGroupHeader group_header(const void* table) {      // the fields the kernels use
+  const __attribute__((address_space(4))) int* w = (const __attribute__((address_space(4))) int*)(uintptr_t)table;
+  MvGroupHeader h = {};
+  h.count = w[1]; h.units = w[4]; h.direct = w[5]; h.tail = w[6]; h.split = w[7];
+  return h;
+}
+template <int NJ, int WN, int NSTAGE, bool F16 = false>
+__global__ __launch_bounds__(128 * WN, 1) void gemm_pring_grouped_kernel(GroupArgs ga, int units) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr bool TA = true, TB = true;
+  constexpr int KS = 2;
+  constexpr int NW = 2 * WN;
+  constexpr int BN = WN * 16 * NJ;
+  constexpr bool BP512 = BN > 128;
+  constexpr int BKS = G2_BK * KS;
+  constexpr int A_BYTES = 16384 * KS;
+  constexpr int B_BYTES = (BP512 ? 16384 : 8192) * KS;
+  constexpr int STAGE = A_BYTES + B_BYTES;
+  constexpr int LPS = STAGE / 1024 / NW;
+  constexpr int EPI_OPS = 28;
+  static_assert(BN == MV_GROUP_TILE && G2_BM == MV_GROUP_TILE && BKS == MV_GROUP_BK, "the table's units are 256 x 256 tiles, 64-deep stages");
+  static_assert(NW * 4608 <= STAGE, "epilogue scratch must fit in one ring stage");
+  static_assert((NSTAGE - 2) * LPS + EPI_OPS < 64, "vmcnt is a 6-bit counter");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, lq = lane >> 4;
+  const int wm = (wid / WN) * 128, wn = (wid % WN) * (16 * NJ);
+  const int G = gridDim.x;
+  const MvGroupHeader h = group_header(ga.table);
+  const group_tab_t tab = (group_tab_t)((uintptr_t)ga.table + sizeof(MvGroupHeader));
 
-#define LAUNCH_PRING(TA_, TB_, NJ_, WN_, NS_, F16_)                                                                  \
+  // issue cursor: runs NSTAGE-1 stages ahead of the compute cursor, across unit (and problem) boundaries
+  int iu = blockIdx.x, is = 0, im0 = 0, in0 = 0, ik0 = 0, ikend = 0, inst = 0, ilda = 0, ildb = 0, iM = 0, iN = 0;
+  unsigned ibA = 0, ibB = 0;
+  dma_rsrc_t rsA = {0, 0, 0, 0}, rsB = {0, 0, 0, 0};
+  unsigned ifs = 0, cfs = 0;
+  auto issue_unit = [&]() {
+    const MvGroupUnit d = mv_group_decode(h, tab, iu);
+    const group_tab_t e = tab + d.problem;
+    im0 = d.m0; in0 = d.n0; ik0 = d.kbeg; ikend = d.kend;
+    inst = max(1, (d.kend - d.kbeg + BKS - 1) / BKS);        // an empty slice still runs one (all-zero) stage
+    ilda = e->lda; ildb = e->ldb; iM = e->M; iN = e->N; ibA = e->bytesA; ibB = e->bytesB;
+    rsA = dma_rsrc(e->A, ibA);
+    rsB = dma_rsrc(e->B, ibB);
+  };
+  if (iu < units) issue_unit();
+  auto issue_one = [&]() {
+    if (iu >= units) return;
+    char* st = smem + (ifs % NSTAGE) * STAGE;
+    const int k0 = ik0 + is * BKS;
+    g2_issue<TA, true, A_BYTES / 1024, NW, KS>(rsA, ibA, ilda, im0, iM, G2_BM, k0, ikend, st, wid, lane);
+    g2_issue<TB, BP512, B_BYTES / 1024, NW, KS>(rsB, ibB, ildb, in0, iN, BN, k0, ikend, st + A_BYTES, wid, lane);
+    ++ifs;
+    if (++is == inst) {
+      iu += G; is = 0;
+      if (iu < units) issue_unit();
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < NSTAGE - 1; ++i) issue_one();
+
+  int epi_ops = 0;
+  for (int cu = blockIdx.x; cu < units; cu += G) {
+    const MvGroupUnit d = mv_group_decode(h, tab, cu);
+    const int nst = max(1, (d.kend - d.kbeg + BKS - 1) / BKS);
+    f32x4 acc[8][NJ];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    for (int s = 0; s < nst; ++s) {
+      const int younger = (int)(ifs - cfs) - 1;
+      const bool after_epi = (s == 0) && epi_ops > 0;
+      if (after_epi) {
+        if (NSTAGE > 2 && younger >= 1) wait_vmcnt<(NSTAGE > 2 ? LPS : 0) + EPI_OPS>();
+        else wait_vmcnt<EPI_OPS>();
+      } else {
+        if (NSTAGE > 2 && younger >= 1) wait_vmcnt<(NSTAGE > 2 ? LPS : 0)>();
+        else wait_vmcnt<0>();
+      }
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      issue_one();
+      const char* tA = smem + (cfs % NSTAGE) * STAGE;
+      const char* tB = tA + A_BYTES;
+      g2_stage_mma_tr<TA, TB, BP512, NJ, KS, F16>(tA, tB, wm, wn, l15, lq, acc);
+      ++cfs;
+    }
+
+    __builtin_amdgcn_s_barrier();
+    char* scr = smem + ((cfs + NSTAGE - 1) % NSTAGE) * STAGE + wid * 4608;
+    const int rrow = lane >> 4, c4 = lane & 15;
+    const bool col_on = (c4 * 4) < 16 * NJ;
+    constexpr int G2_NI = 8;
+    GemmArgs p = {};
+    p.c_dtype = MV_F32; p.epi = MV_EPI_NONE; p.alpha = ga.alpha; p.accumulate = ga.accumulate;
+    if (d.slice >= 0) {       // a K-slice of a tail tile: the whole 256 x 256 partial tile goes to its slab (rows / columns past the matrix are zeros)
+      p.M = MV_GROUP_TILE; p.N = MV_GROUP_TILE; p.splitk = h.split;
+      p.ws = ga.ws + (size_t)(d.tile - h.direct) * h.split * (MV_GROUP_TILE * MV_GROUP_TILE);
+      const int split = d.slice, m0 = 0, n0 = 0;
+      G2_EPI_BODY(-1)
+      epi_ops = EPI_OPS;
+    } else {
+      const group_tab_t e = tab + d.problem;
+      p.C = e->C; p.ldc = e->ldc; p.M = e->M; p.N = e->N; p.splitk = 1;
+      p.vec_ok = ((p.ldc & 3) == 0) && ((((uintptr_t)p.C) & 15) == 0);
+      const int split = 0, m0 = d.m0, n0 = d.n0;
+      G2_EPI_BODY(MV_EPI_NONE)
+      const bool full = (m0 + G2_BM <= p.M) && (n0 + BN <= p.N) && ((p.N & 3) == 0) && p.vec_ok;
+      epi_ops = full ? EPI_OPS : 0;
+    }
+  }
+}
+
+#define LAUNCH_PRING(TA_, TB_, NJ_, WN_, NS_, F16_)                                                                 \
   do {                                                                                                               \
     constexpr size_t shm = (size_t)(NS_) * 2 * (16384 + ((WN_) * 16 * (NJ_) > 128 ? 16384 : 8192));                  \
     static bool attr_set = false;                                                                                    \

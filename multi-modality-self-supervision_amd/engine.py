@@ -221,6 +221,15 @@ class Engine:
         self._w2t, self._w2t_ev, self._w2t_stale = None, None, True
         self.head_on_side = True  # the tied decoder's weight gradient on the side stream (see _mlm_backward)
         self.fused_colsum = os.environ.get("MV_FUSED_COLSUM", "1") != "0"   # bias gradients from partial sums of the producing kernels
+        # the weight gradients of all full-row layers in ONE persistent launch over full contractions instead of four split-K launches
+        # (+ four reductions) per layer (include/medvill.h, mv_gemm_grouped_tn).  Undistributed steps only: under a
+        # bucket_hook every layer's gradients must be final when its bucket is handed over.  MV_GROUPED_DW=0: the per-layer path.
+        self.grouped_dw = os.environ.get("MV_GROUPED_DW", "1") != "0"
+        # MV_GROUPED_DW_PARTS=n: the deferred layers in n launches, each as soon as its last operand exists (1: one launch behind the
+        # whole backward).  0, the default: two layers per launch -- 216 full-K tiles, one round of blocks with no slab, and the main
+        # chain's LayerNorm / attention kernels of the next layers still run beside it (1 / 2 / 3 / 4 / 6 launches measured)
+        self.grouped_dw_parts = max(0, int(os.environ.get("MV_GROUPED_DW_PARTS", "0")))
+        self._dw_group = {}
         self.head_params_on_side = True   # MLM head: decoder-bias column sums and the transform's parameter gradients on the side stream
         self.late_opt_wait = True     # the forward's preparation kernels run under the optimizer's first kernel (encoder_forward)
         self.itm_on_side = True       # ITM head on the side stream under the MLM head's decoder GEMM (heads_train)
@@ -298,6 +307,7 @@ class Engine:
         self._ws.clear()
         self.shadow_dirty = True
         self._gemm_ws = {}
+        self._dw_group = {}
         self._bind()
         return self
 
@@ -932,6 +942,37 @@ class Engine:
                 self.refresh_w2t(on_side=False)
             main.wait_event(self._w2t_ev)
         pd, dk = S["p_drop"], S["drop_keys"]
+        # deferred weight gradients (see grouped_dw): (dy, x, gW, No, Ko, rows, lda, ldb, ldc) of the full-row layers
+        group = [] if (self.grouped_dw and bucket_hook is None and self.is16 and ops.get_impl() == 0 and H % 8 == 0 and I % 8 == 0) else None
+
+        def dW(defer, dy_, x_, gW_, No, Ko, rows, lda, ldb):
+            if defer:
+                group.append((dy_, x_, gW_, No, Ko, rows, lda, ldb, Ko))
+            else:
+                fork()
+                with torch.cuda.stream(side):
+                    self._dW(dy_, x_, gW_, No, Ko, rows, lda=lda, ldb=ldb)
+
+        # the deferred layers go in grouped_dw_parts launches; a part is launched (on the side stream) behind the attention backward of
+        # its last layer, so the main chain's remaining VALU- and HBM-bound kernels still run beside it
+        full = [l for l in reversed(range(cfg.layers)) if S["layers"][l]["rows"] == M]
+        parts = min(self.grouped_dw_parts or (len(full) + 1) // 2, max(len(full), 1))
+        flush_after = {full[(len(full) * (i + 1) + parts - 1) // parts - 1]: i for i in range(parts)} if (group is not None and full) else {}
+
+        def flush(part):
+            # every deferred operand outlives the layer loop: the per-layer scratch of this backward and the activations the forward
+            # kept -- never one of the buffers the loop rewrites layer after layer
+            shared = {t.data_ptr() for t in (dctx, da, dxb[0], dxb[1])} | {self._ws[k].data_ptr() for k in ("bw_dctx_tail", "bw_dx_unperm") if k in self._ws}
+            operands = [t.data_ptr() for q in group for t in q[:3]]
+            assert len(set(operands)) == len(operands) and not (shared & set(operands)), "grouped dW: an operand is not a per-layer buffer"
+            tab = self._dw_group.get(part)
+            if tab is None:
+                tab = self._dw_group[part] = ops.GroupedTN(self.device)
+            tab.set(adt, group)      # rebuilt and uploaded only when a pointer or a row count changed
+            wb = tab.workspace_bytes()
+            tab.launch(ws=self._gemm_workspace(wb // 4) if wb else None, alpha=us)
+            group.clear()
+
         dctx = self._buf("bw_dctx", (M, H), adt)
         delta = self._buf("bw_delta", (B, A, Lq), torch.float32)
         da = self._buf("bw_da", (M, H), adt)
@@ -957,9 +998,8 @@ class Engine:
                               g[p + "output.LayerNorm.weight"], g[p + "output.LayerNorm.bias"], g[p + "output.dense.bias"], M, H,
                               dx_drop=dprd2, p_drop=pd, drop_key=dk[(self.SITE_OUT2, l)], unscale=us)
             dproj2 = dprd2 if dprd2 is not None else dpre2
-            fork()
-            with torch.cuda.stream(side):
-                self._dW(dproj2, a_["i"], g[p + "output.dense.weight"], H, I, M, lda=H, ldb=I)
+            defer = group is not None and not tail
+            dW(defer, dproj2, a_["i"], g[p + "output.dense.weight"], H, I, M, H, I)
             # FFN-up bias gradient without a second pass over dz: the dz GEMM leaves partial column sums (one row per 128-row tile
             # half) that one small kernel folds (MV_FUSED_COLSUM=0: the column-sum kernel).  The same for dqkv from the attention
             # backward was built and measured slower (profiles/r03_notes.txt): +80 us on the two kernels for 11 us saved.
@@ -977,7 +1017,10 @@ class Engine:
                     ops.colsum_partials(dz_part, dz_part.shape[0], I, I, g[p + "intermediate.dense.bias"], unscale=us)
                 else:
                     ops.colsum(dz, I, M, I, g[p + "intermediate.dense.bias"], accumulate=True, unscale=us)
-                self._dW(dz, a_["a"], g[p + "intermediate.dense.weight"], I, H, M, lda=I, ldb=H)
+                if defer:
+                    group.append((dz, a_["a"], g[p + "intermediate.dense.weight"], I, H, M, I, H, H))
+                else:
+                    self._dW(dz, a_["a"], g[p + "intermediate.dense.weight"], I, H, M, lda=I, ldb=H)
             ops.gemm(dz, self.w[p + "intermediate.dense.weight"], da, tb=True, M=M, N=H, K=I, epi=EPI_RES, r=dpre2)
             # LN1 backward (+ bias grad of attention.output.dense)
             ops.layernorm_bwd(da, a_["pre1"], a_["mean1"], a_["rstd1"], self.p[p + "attention.output.LayerNorm.weight"], dpre1,
@@ -985,9 +1028,7 @@ class Engine:
                               g[p + "attention.output.dense.bias"], M, H, dx_drop=dprd1, p_drop=pd,
                               drop_key=dk[(self.SITE_OUT1, l)], unscale=us)
             dproj1 = dprd1 if dprd1 is not None else dpre1
-            fork()
-            with torch.cuda.stream(side):
-                self._dW(dproj1, a_["ctx_tail"] if tail else a_["ctx"], g[p + "attention.output.dense.weight"], H, H, M, lda=H, ldb=H)
+            dW(defer, dproj1, a_["ctx_tail"] if tail else a_["ctx"], g[p + "attention.output.dense.weight"], H, H, M, H, H)
             if tail:
                 # d(ctx) exists on the consumed rows only: everywhere else it is exactly zero
                 dctx_s = self._buf("bw_dctx_tail", (M, H), adt)
@@ -1003,7 +1044,12 @@ class Engine:
             fork()
             with torch.cuda.stream(side):
                 ops.colsum(dqkv, 3 * H, M, 3 * H, gbqkv, accumulate=True, unscale=us)
-                self._dW(dqkv, a_["x"], gWqkv, 3 * H, H, M, lda=3 * H, ldb=H)
+                if defer:
+                    group.append((dqkv, a_["x"], gWqkv, 3 * H, H, M, 3 * H, H, H))
+                    if l in flush_after:
+                        flush(flush_after[l])
+                else:
+                    self._dW(dqkv, a_["x"], gWqkv, 3 * H, H, M, lda=3 * H, ldb=H)
                 ev_layer = side_done()
             dx = dxb[l & 1]          # never the buffer dy currently lives in
             if tail:

@@ -2,6 +2,8 @@
 and streams only; every wrapper enqueues on torch's current stream and returns immediately."""
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib as L
@@ -490,6 +492,82 @@ def gemm_workspace_bytes(dtype, ta, tb, M, N, K) -> int:
 def workspace_bytes(hidden, intermediate, vocab, img_hidden, max_rows, max_label_rows, max_regions) -> int:
     """The largest split-K workspace any GEMM of a pretraining step asks for at this geometry (mv_workspace_bytes)."""
     return int(_lib().mv_workspace_bytes(int(hidden), int(intermediate), int(vocab), int(img_hidden), int(max_rows), int(max_label_rows), int(max_regions)))
+
+
+class GroupProblem(ctypes.Structure):
+    """include/medvill.h: mv_group_problem -- C[No, Ko] (+)= alpha * A[rows, No]^T . B[rows, Ko]."""
+    _fields_ = [("A", L.vp), ("B", L.vp), ("C", L.vp), ("lda", L.i32), ("ldb", L.i32), ("ldc", L.i32), ("No", L.i32), ("Ko", L.i32),
+                ("rows", L.i32)]
+
+
+class GroupedTN:
+    """The problem table of mv_gemm_grouped_tn: a host copy (what the library validates and plans the grid from) and a device copy (all
+    the kernels read; the library cannot check it, so it is only ever written from the host copy, right after that was filled).  set()
+    rebuilds both only when a problem changed: a loop over batches of one shape copies nothing per step, one whose packed row count
+    changes from batch to batch refills the table (a few KiB through one pinned staging buffer) on every step."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.key = None
+        self.count = 0
+        self.dtype = 0
+        self.host = None          # ctypes buffer
+        self.dev = None           # uint8 tensor
+        self.staged = None        # pinned uint8 tensor the upload reads, and the event after its last upload
+        self.staged_ev = None
+        self.uploads = 0          # times the table was rebuilt and copied to the device
+        self.launches = 0
+
+    def set(self, dtype, problems, n_blocks=0):
+        """problems: (a, b, c, No, Ko, rows, lda, ldb, ldc) with tensors a [rows, lda], b [rows, ldb] (16-bit), c f32 [No, ldc].  Returns True
+        when the table was rebuilt (and enqueues its upload on the current stream)."""
+        dt = dtype if isinstance(dtype, int) else L.dt_of(torch.empty(0, dtype=dtype))
+        key = (dt, int(n_blocks), L.get_knob("persistent_cus"),
+               tuple((a.data_ptr(), b.data_ptr(), c.data_ptr(), No, Ko, rows, lda, ldb, ldc) for a, b, c, No, Ko, rows, lda, ldb, ldc in problems))
+        if key == self.key:
+            return False
+        for a, b, c, *_ in problems:
+            L.require_cuda(a, b, c)
+            if L.dt_of(a) != dt or L.dt_of(b) != dt or c.dtype != torch.float32:
+                raise TypeError("grouped dW: 16-bit operands of one encoding, f32 outputs")
+        n = len(problems)
+        arr = (GroupProblem * max(n, 1))(*[GroupProblem(k[0], k[1], k[2], k[6], k[7], k[8], k[3], k[4], k[5]) for k in key[3]])
+        nbytes = int(_lib().mv_gemm_grouped_table_bytes(n))
+        host = self.host if self.host is not None and len(self.host) >= nbytes else ctypes.create_string_buffer(max(nbytes, 1))
+        self.key = None           # a failed fill leaves no table behind
+        L.check(_lib().mv_gemm_grouped_fill(dt, n, arr, int(n_blocks), host, nbytes), f"mv_gemm_grouped_fill(count={n})")
+        if self.staged is None or self.staged.numel() < nbytes:
+            self.staged = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+            self.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        elif self.staged_ev is not None:
+            self.staged_ev.synchronize()      # the previous upload has read the staging buffer
+        ctypes.memmove(self.staged.data_ptr(), host, nbytes)
+        self.dev[:nbytes].copy_(self.staged[:nbytes], non_blocking=True)
+        self.staged_ev = torch.cuda.Event()
+        self.staged_ev.record()
+        self.host, self.key, self.count, self.dtype = host, key, n, dt
+        self.uploads += 1
+        return True
+
+    def workspace_bytes(self) -> int:
+        return int(_lib().mv_gemm_grouped_workspace_bytes(self.host))
+
+    def units(self):
+        """Every launch unit as (problem, m0, n0, kbeg, kend, slice, tile) -- the kernel's own map (mv_gemm_grouped_decode)."""
+        hdr = (ctypes.c_int * 16).from_buffer(self.host)
+        out = (ctypes.c_int * 7)()
+        res = []
+        for u in range(hdr[5] + hdr[6] * hdr[7]):
+            L.check(_lib().mv_gemm_grouped_decode(self.host, u, out), "mv_gemm_grouped_decode")
+            res.append(tuple(out))
+        return res
+
+    def launch(self, ws=None, accumulate=False, alpha=None):
+        L.require_cuda(ws, alpha)
+        rc = _lib().mv_gemm_grouped_tn(self.dtype, self.count, self.host, L.ptr(self.dev), L.ptr(ws), (ws.numel() * 4) if ws is not None else 0,
+                                       int(accumulate), L.ptr(alpha), L.stream_ptr())
+        L.check(rc, f"mv_gemm_grouped_tn(count={self.count})")
+        self.launches += 1
 
 
 def set_gemm_variant(force: int = 0, nj: int = 0):

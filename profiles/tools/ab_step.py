@@ -68,6 +68,13 @@ VARIANTS = {
                ("ring tile height chosen for whole rounds of CUs (320 x 256 tiles: one round at ~25k rows)", lambda: mv.hip_ops.set_gemm_rounds(1))],
     "order": [("attention blocks: row block slowest (rounds 3-4)", lambda: mv.hip_ops.set_attn_order(0)),
               ("attention blocks: a pair's row blocks adjacent on one XCD", lambda: mv.hip_ops.set_attn_order(1))],
+    "grouped": [("weight gradients: four split-K launches + reductions per layer", lambda: setattr(model.engine, "grouped_dw", False)),
+                ("weight gradients: the full-row layers in one full-K grouped launch",
+                 lambda: (setattr(model.engine, "grouped_dw", True), setattr(model.engine, "grouped_dw_parts", 1))),
+                ("weight gradients: full-K grouped launches of two layers each (the default)",
+                 lambda: (setattr(model.engine, "grouped_dw", True), setattr(model.engine, "grouped_dw_parts", 0)))],
+    "gparts": [(f"grouped weight gradients of the full-row layers in {n} launch(es)",
+                (lambda n=n: (setattr(model.engine, "grouped_dw", True), setattr(model.engine, "grouped_dw_parts", n)))) for n in (1, 2, 3, 4, 6, 11)],
     "tail": [("last layer on all rows", lambda: setattr(step, "tail_rows", False)), ("last layer on consumed rows", lambda: setattr(step, "tail_rows", True))],
 }
 def _side_plain():

@@ -8,6 +8,8 @@ cases
   ffn1   the FFN-up projection (256x256 ring kernel, NT form): [32768, 768] x [3072, 768]^T + bias, GELU and GELU' epilogue, two f16 outputs
   attn   attention forward + backward (dQ, dK/dV) at B = 64, A = 12, L = 512, ragged packed rows, dropout 0.1 from keep-bits
   qkv wo ffn2 dz da dctx dxqkv dw2 dwqkv dwo   the other GEMM calls of an encoder layer (GEMM_FAMILY below)
+  dwgroup  the grouped weight-gradient launch alone: dW2, dW1, dWo and dWqkv of the 11 full-row layers (44 products, 1,188 tiles of
+         256 x 256 over full contractions) + the reduction of its tail tiles; not part of `all`
 usage: python3 profiles/tools/dominant.py <case> [reps] [warm-up]   |   python3 profiles/tools/dominant.py all [reps] [warm-up] [out.json]"""
 import os
 import sys
@@ -70,6 +72,22 @@ def make_case(name, dev="cuda"):
         fwd = 4.0 * A * dh * float((vl * vl).sum())
         return fn, dict(kernel=f"attn_dropmask + attn_fwd_mfma + attn_bwd_dq_mfma + attn_bwd_dkv_mfma, B={B} A={A} L={L} rows {M}, dropout 0.1",
                         symbol="attn_", flop=3.5 * fwd, bytes=2.0 * M * (3 * H + H) * 3)
+    if name == "dwgroup":
+        M, layers = ROWS_PACKED, 11
+        alpha = torch.tensor([1.0 / 32768.0], device=dev)
+        probs, flop, byt = [], 0.0, 0.0
+        for l in range(layers):
+            for j, (No, Ko) in enumerate(((H, I), (I, H), (H, H), (3 * H, H))):        # the order Engine.encoder_backward records them in
+                dy, x = _rnd((M, No), 0.1, 60 + 8 * l + 2 * j, dev), _rnd((M, Ko), 1.0, 61 + 8 * l + 2 * j, dev)
+                probs.append((dy, x, torch.zeros((No, Ko), device=dev), No, Ko, M, No, Ko, Ko))
+                flop += 2.0 * M * No * Ko
+                byt += 2.0 * M * (No + Ko) + 4.0 * No * Ko
+        tab = ops.GroupedTN(dev)
+        tab.set(torch.float16, probs)
+        ws = torch.empty(max(tab.workspace_bytes() // 4, 1), device=dev)
+        fn = lambda: tab.launch(ws=ws, alpha=alpha)
+        return fn, dict(kernel=f"gemm_pring_grouped_kernel<TN, 256x256x64, f16 operands> {len(probs)} products of {layers} layers over {M} rows, full K "
+                               "(+ splitk_reduce_grouped_kernel on the tail tiles)", symbol="gemm_pring_grouped_kernel", flop=flop, bytes=byt)
     if name in GEMM_FAMILY:
         return _gemm_family(name, dev)
     raise ValueError(name)
