@@ -99,7 +99,8 @@ int mv_stream_destroy(void* stream);
  * 16-bit operands need 16-byte aligned bases and lda, ldb multiples of 8; a contraction length
  * K that is not a multiple of 8 is allowed only when the k-contiguous operand's rows are
  * zero-padded up to the next multiple of 8.
- * splitk = 0: let the library pick (up to 32 slices, as many as ws holds; without ws 1 is used).
+ * splitk = 0: let the library pick (up to 32 slices on the 256-row kernels, as many as ws holds; up to 16 on the 128x128
+ * kernel, which takes its whole wish or, when ws is smaller than that, 1; without ws 1 is used).
  * splitk > 1: the K range is cut in `splitk` slices whose partial tiles go to `ws`
  * (>= splitk*M*N floats) and are summed by a second kernel; only with MV_EPI_NONE and an f32 C.
  * accumulate != 0: C += result (f32 C, MV_EPI_NONE only).
@@ -123,7 +124,8 @@ int mv_gemm(int dtype, int ta, int tb, int M, int N, int K,
 /* Split-K workspace sizes (SURVEY 8b's mv_workspace_bytes): what a host needs to allocate without reading the dispatch code.
  *   mv_gemm_workspace_bytes  bytes of `ws` with which mv_gemm(splitk = 0) takes the split-K choice it prefers for this product
  *                            (slabs x M x N x 4; 0 = this call never splits: f32 data, a wide / large product, K < 2048).  A smaller
- *                            workspace is legal: mv_gemm then takes as many slabs as fit.
+ *                            workspace is legal: the 256-row kernels then take as many slabs as fit, the 128x128 kernel does
+ *                            not split (one slab).
  *   mv_workspace_bytes       the largest such workspace any mv_gemm call of a pretraining step asks for at this geometry (weight
  *                            gradients of the four encoder projections, of the MLM transform and of the image projection over
  *                            `max_rows` / `max_label_rows` / `max_regions` rows; the tied decoder's input gradient over the

@@ -328,6 +328,7 @@ __global__ void splitk_reduce_kernel(GemmArgs p) {
         for (int k = 0; k < p.splitk; ++k) s += p.ws[k * mn + e + j];
         const int m = (int)((e + j) / p.N), n = (int)((e + j) - (size_t)m * p.N);
         float* c = (float*)p.C + (size_t)m * p.ldc + n;
+        if (p.alpha) s *= *p.alpha;
         *c = p.accumulate ? *c + s : s;
       }
     }
@@ -361,7 +362,7 @@ static int gemm_n_cu() {
   }();
   return n;
 }
-static GemmRoute gemm_route(int ta, int tb, int M, int N, int K, int splitk, bool rows256 = false) {      // rows256: the caller needs 256-row tiles (fused column sums)
+static GemmRoute gemm_route(int ta, int tb, int M, int N, int K, int splitk, bool f16, bool rows256 = false) {      // rows256: the caller needs 256-row tiles (fused column sums)
   GemmRoute r;
   const int tm2 = (M + 255) / 256;
   const long long t256 = (long long)tm2 * ((N + 255) / 256), t128 = (long long)tm2 * ((N + 127) / 128);
@@ -403,6 +404,7 @@ static GemmRoute gemm_route(int ta, int tb, int M, int N, int K, int splitk, boo
     // tiles) gain 5-8 % from the persistent form; y = x.W^T does not (profiles/r01_gemm_variants.txt)
     r.variant = g_mv_gemm_nj ? g_mv_gemm_nj : (ta ? 24 : 14);        // (knob: 14, 24, 10 = 320-row tiles or 2 = 256x128 tiles, 4 waves, two blocks per CU)
     if (r.variant == 10 && ta) r.variant = 24;                      // the 320-row form exists for y = x.W^T and dx = dy.W
+    if (r.variant == 2 && !(f16 && ta == tb)) r.variant = ta ? 24 : 14;   // the 256x128 form exists for f16 operands of y = x.W^T and dW = dy^T.x
     const bool v128 = r.variant == 2;
     r.tiles = v128 ? t128 : (r.variant == 10 ? (long long)((M + 319) / 320) * ((N + 255) / 256) : t256);
     const long long slots = v128 ? 512 : 256;
@@ -417,7 +419,7 @@ static GemmRoute gemm_route(int ta, int tb, int M, int N, int K, int splitk, boo
 
 extern "C" size_t mv_gemm_workspace_bytes(int dtype, int ta, int tb, int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0 || !mv_is16(dtype) || g_mv_impl != 0) return 0;      // split-K is chosen on the MFMA kernels only
-  const GemmRoute r = gemm_route(ta, tb, M, N, K, 0);
+  const GemmRoute r = gemm_route(ta, tb, M, N, K, 0, dtype == MV_F16);
   return r.sk_auto > 1 ? (size_t)r.sk_auto * (size_t)M * (size_t)N * sizeof(float) : 0;
 }
 
@@ -499,7 +501,7 @@ extern "C" int mv_gemm(int dtype, int ta, int tb, int M, int N, int K, const voi
     if (bytesA >= 0x7fffffffULL || bytesB >= 0x7fffffffULL) return MV_E_SHAPE;
     p.bytesA = (unsigned)bytesA; p.bytesB = (unsigned)bytesB;
     // tile choice (gemm_route): a 256-row ring kernel when it fills the chip, the 128x128 kernel for small problems, dx and 768-column outputs
-    const GemmRoute route = gemm_route(ta, tb, M, N, K, splitk, colsum_part != nullptr);
+    const GemmRoute route = gemm_route(ta, tb, M, N, K, splitk, f16, colsum_part != nullptr);
     const bool big = route.big;
     if (big) {
       const int variant = route.variant;
