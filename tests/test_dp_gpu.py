@@ -1,6 +1,7 @@
 """Data-parallel step on the GPU box: two ranks (gloo transport, both on cuda:0 -- the box has one GPU; RCCL needs
 one device per rank) run TrainStep(distributed=True) on the two halves of a global mini-batch; the result must equal
 the single-process step on the whole mini-batch (global loss normalisation + summed gradients)."""
+import gc
 import os
 import socket
 
@@ -10,6 +11,20 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 pytestmark = pytest.mark.gpu
+
+
+def _manager():
+    """mp.Manager() whose server process -- a fork of this one, which holds an initialised GPU runtime -- never finalises an object it
+    inherited: cyclic garbage left by earlier tests (events, streams, device tensors) is collected HERE first, and what is alive is frozen
+    across the fork.  Without this the server's own garbage collector can pick such garbage up and run its destructors in the forked child,
+    where the GPU runtime is not usable: seen once as a segmentation fault of the server while it pickled a result ("Garbage-collecting" in
+    its traceback), which the test then reports as EOFError."""
+    gc.collect()
+    gc.freeze()
+    try:
+        return mp.Manager()
+    finally:
+        gc.unfreeze()
 
 
 def _free_port():
@@ -53,7 +68,7 @@ def _worker(rank, world, port, out, dtype, train_mode):
 def test_two_rank_step_equals_single_process_step(dtype):
     """fp32: exact path, padded rows.  bf16: the 16-bit path with packed rows (mixed full / seq2seq masks)."""
     world = 2
-    mgr = mp.Manager()
+    mgr = _manager()
     out = mgr.dict()
     mp.spawn(_worker, args=(world, _free_port(), out, dtype, False), nprocs=world, join=True)
     mv, cfg, m = _model(dtype)
@@ -75,7 +90,7 @@ def test_two_rank_step_equals_single_process_step(dtype):
 
 def test_two_rank_training_mode_draws_rank_local_dropout_and_keeps_replicas_identical():
     world = 2
-    mgr = mp.Manager()
+    mgr = _manager()
     out = mgr.dict()
     mp.spawn(_worker, args=(world, _free_port(), out, torch.bfloat16, True), nprocs=world, join=True)
     assert torch.equal(out[0][0], out[1][0]) and bool(torch.isfinite(out[0][0]).all())
@@ -101,7 +116,7 @@ def _bad_seed_worker(rank, world, port, out):
 
 def test_replicas_with_different_parameters_are_refused():
     world = 2
-    mgr = mp.Manager()
+    mgr = _manager()
     out = mgr.dict()
     mp.spawn(_bad_seed_worker, args=(world, _free_port(), out), nprocs=world, join=True)
     assert all("different parameters" in out[r] for r in range(world)), dict(out)
@@ -134,7 +149,7 @@ def test_two_rank_step_over_rccl():
     """The same two-rank step over the nccl backend (= RCCL over xGMI), one device per rank, bf16 path, dropout on, packed rows,
     bucketed gradient all-reduce on the side stream: replicas must stay bit-identical and finite."""
     world = 2
-    mgr = mp.Manager()
+    mgr = _manager()
     out = mgr.dict()
     mp.spawn(_rccl_worker, args=(world, _free_port(), out), nprocs=world, join=True)
     assert torch.equal(out[0][0], out[1][0]) and bool(torch.isfinite(out[0][0]).all())
@@ -174,7 +189,7 @@ def test_one_rank_rccl_group_runs_every_collective():
     the per-step count all-reduce and the bucketed gradient all-reduces on the communication stream all go through RCCL.  Summing
     over one rank changes nothing: the parameters must follow the undistributed step (up to the float-atomic noise of the
     gradients, see test_overlapped_optimizer_equals_the_plain_step)."""
-    mgr = mp.Manager()
+    mgr = _manager()
     out = mgr.dict()
     mp.spawn(_rccl_one_rank_worker, args=(1, _free_port(), out), nprocs=1, join=True)
     (p_d, s_d, exposed, nb, timeline, env), (p_s, s_s, _, _, tl_s, _) = out[0]
@@ -230,7 +245,7 @@ def test_one_rank_failing_its_mask_check_changes_no_collective():
     that step on the matrix while its peer runs on descriptors.  Uneven evaluation loaders (no collective in evaluation) and two
     epochs: nothing hangs, the replicas stay identical."""
     world = 2
-    mgr = mp.Manager()
+    mgr = _manager()
     out = mgr.dict()
     mp.spawn(_trainer_worker, args=(world, _free_port(), out), nprocs=world, join=True)
     (p0, rec0, rej0, d0, l0), (p1, rec1, rej1, d1, l1) = out[0], out[1]
@@ -276,7 +291,7 @@ def test_c_abi_rccl_communicator_on_one_rank(tmp_path):
     """mv_comm_* (SURVEY 8b's export list): the C ABI's own RCCL binding, bound at run time.  A one-rank communicator on this one-GPU box
     (the sum over one rank is the identity) exercises id creation, init, asynchronous all-reduce on a side stream, the device-side wait and
     destroy through RCCL itself; the two-rank form below runs wherever two GPUs are visible."""
-    mgr = mp.Manager()
+    mgr = _manager()
     out = mgr.dict()
     mp.spawn(_comm_abi_worker, args=(1, str(tmp_path / "uid0"), out), nprocs=1, join=True)
     assert max(out[0]) < 1e-6, out[0]
@@ -284,7 +299,7 @@ def test_c_abi_rccl_communicator_on_one_rank(tmp_path):
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="RCCL needs one device per rank: runs on nodes with >= 2 GPUs")
 def test_c_abi_rccl_communicator_on_two_ranks(tmp_path):
-    mgr = mp.Manager()
+    mgr = _manager()
     out = mgr.dict()
     mp.spawn(_comm_abi_worker, args=(2, str(tmp_path / "uid"), out), nprocs=2, join=True)
     assert max(out[0]) < 1e-2 and max(out[1]) < 1e-2, dict(out)
