@@ -16,7 +16,46 @@ feed those scripts, and the inverse maps let their checkpoints come back.
 """
 from __future__ import annotations
 
+import json
+import os
 from collections import OrderedDict
+
+import torch
+
+WEIGHTS_NAME = "pytorch_model.bin"
+
+
+def hf_config(cfg, architecture, **extra):
+    """The config.json of a model of geometry `cfg` (engine.ModelConfig), HF BertConfig names; `extra`: the task's own entries, last."""
+    return dict(architectures=[architecture], model_type="bert", vocab_size=cfg.vocab_size, hidden_size=cfg.hidden,
+                num_hidden_layers=cfg.layers, num_attention_heads=cfg.heads, intermediate_size=cfg.intermediate,
+                max_position_embeddings=cfg.max_pos, type_vocab_size=cfg.type_vocab, layer_norm_eps=cfg.ln_eps, hidden_act="gelu",
+                hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, **extra)
+
+
+def write_pretrained(directory, config_dict, state_dict):
+    """HF layout: config.json + pytorch_model.bin (train_origin.py:254-266)."""
+    os.makedirs(directory, exist_ok=True)
+    with open(os.path.join(directory, "config.json"), "w") as f:
+        json.dump(config_dict, f, indent=2)
+    torch.save({k: v.cpu() for k, v in state_dict.items()}, os.path.join(directory, WEIGHTS_NAME))
+
+
+def read_config(directory):
+    with open(os.path.join(directory, "config.json")) as f:
+        return json.load(f)
+
+
+def read_pretrained(path_or_state_dict, config=None):
+    """A checkpoint directory (its config.json is read unless `config` is given) or a state dict (then `config` is required)
+    -> (config, state dict)."""
+    if not isinstance(path_or_state_dict, (str, os.PathLike)):
+        if config is None:
+            raise ValueError("from_pretrained(state_dict): pass config= as well")
+        return config, path_or_state_dict
+    if config is None:
+        config = read_config(path_or_state_dict)
+    return config, torch.load(os.path.join(path_or_state_dict, WEIGHTS_NAME), map_location="cpu")
 
 
 def to_finetune_keys(state_dict):

@@ -10,24 +10,22 @@
 
 The encoder runs its last layer's per-row work on the B [CLS] rows only (Engine.encoder_forward, tail_rows=[]), as VQA training; the
 engine's pooler feeds `clf`; unlike VQA the pooler gets a gradient (Engine._pooler_backward), the ITM and MLM heads get none.  `clf`
-lives in a small flat buffer of its own with C padded to a multiple of 16 (padding rows stay zero), the scheme and the storage helpers
-of the VQA head -- hence the base class.  Arithmetic is CXRBERT's (the pretrained model), DESIGN.md "8c".
+lives in a small flat buffer of its own with C padded to a multiple of 16 (padding rows stay zero): task.FlatHead, as the VQA head.
+Arithmetic is CXRBERT's (the pretrained model), DESIGN.md "8c".
 """
 from __future__ import annotations
 
-import json
-import os
-import weakref
 from collections import OrderedDict
-from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
 from . import hip_ops as ops
 from ._lib import EPI_BIAS
-from .cxrbert import CXRBERT, _hand_over_grads, _holds_views, _use_views
-from .vqa import CXRBertForVQA, _ROWS
+from .checkpoint import hf_config, read_pretrained, write_pretrained
+from .cxrbert import run_backward
+from .task import FlatHead, check_single_rank
+from .vqa import _ROWS
 
 CLF_KEYS = ("clf.weight", "clf.bias")
 
@@ -40,13 +38,6 @@ def clf_layout(H: int, C: int):
         lay[name] = (off, shape)
         off += (n + 63) // 64 * 64
     return lay, off, Cp
-
-
-def _check_single_rank():
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise RuntimeError("CXRBertForClassification: data-parallel fine-tuning is not supported (the head's gradients would not be "
-                           "all-reduced); fine-tune on one rank, or run inference under torch.no_grad()")
 
 
 class _ClfFn(torch.autograd.Function):
@@ -69,34 +60,15 @@ class _ClfFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         model = ctx.model
-        bert = model.bert
-        eng = bert.engine
-        views = _use_views(bert)
-        held = eng.flat_g.clone() if (views and eng.flat_g is not None and _holds_views(bert)) else None
-        held_h = model.head_g.clone() if (views and model.head_g is not None and model._head_holds_views()) else None
-        model._backward_once(ctx, g)
-        if eng.scaler is not None:               # f16 gradients: an overflow (the head's buffer included) is redone with S / 16, as VQA
-            for _ in range(8):
-                eng.scaler[6:7].zero_()
-                ops.count_nonfinite(eng.flat_g, eng.scaler[6:7])
-                ops.count_nonfinite(model.head_g, eng.scaler[6:7])
-                if float(eng.scaler[6]) == 0.0:
-                    break
-                eng.reset_scaler(max(float(eng.scaler[0]) / 16.0, 1.0))
-                model._backward_once(ctx, g)
-        if held is not None:
-            eng.flat_g.add_(held)
-        if held_h is not None:
-            model.head_g.add_(held_h)
-        return (None,) * 10 + _hand_over_grads(bert) + model._hand_over_head(views)
+        return (None,) * 10 + run_backward(model.bert, lambda: model._backward_once(ctx, g), head=model)
 
 
-class CXRBertForClassification(CXRBertForVQA):
+class CXRBertForClassification(FlatHead):
     """forward(cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, labels=None):
          labels None -> differentiable f32 logits [B, C];  labels [B, C] multi-hot float -> the mean BCEWithLogitsLoss (with
          `pos_weight` when set), and `model.clf_stats` f32 [3, C] on the device += {tp, fp, fn} at threshold 0.5 (reset_stats() clears).
     .bert is the CXRBERT (its pooler is the head's first half), .clf the Linear(H, C) whose Parameters are views of the head's flat
-    buffer.  (Subclass of CXRBertForVQA for the head's storage, hand-over and device-move helpers only; every task method is its own.)"""
+    buffer (task.FlatHead)."""
 
     _head_keys = CLF_KEYS
     _padded_key = CLF_KEYS[0]
@@ -105,35 +77,17 @@ class CXRBertForClassification(CXRBertForVQA):
     def __init__(self, config, args=None, n_classes=14, pos_weight=None, task_type="multilabel", **kw):
         if task_type != "multilabel":
             raise NotImplementedError(f"task_type={task_type!r}: only the multi-label task (the reference's default) is built")
-        nn.Module.__init__(self)
-        self.bert = CXRBERT(config, args, **kw)
-        self._init_head(int(n_classes))
+        super().__init__(config, args, **kw)
+        H, C = self.bert.cfg.hidden, int(n_classes)
+        if C <= 0:
+            raise ValueError("n_classes must be positive")
+        self.n_classes = C
+        self.clf = nn.Linear(H, C)
+        self.clf_stats = None
+        self._init_head(clf_layout(H, C))
         self.pos_weight = None
         if pos_weight is not None:
             self.set_pos_weight(pos_weight)
-
-    def _init_head(self, C):
-        eng = self.bert.engine
-        H = self.bert.cfg.hidden
-        if C <= 0:
-            raise ValueError("n_classes must be positive")
-        self.n_classes = self.n_answers = C
-        self._layout, self._n_head, self.Ap = clf_layout(H, C)
-        dev = eng.device
-        self.head_p = torch.zeros(self._n_head, dtype=torch.float32, device=dev)
-        self.head_g = self.head_m = self.head_v = None
-        self.head_sh = torch.zeros(self._n_head, dtype=torch.bfloat16, device=dev) if eng.shadow is not None else None
-        self.head_shf = torch.zeros(self._n_head, dtype=torch.float16, device=dev) if eng.shadow_f is not None else None
-        self.clf = nn.Linear(H, C)
-        self._hplist = []
-        for name in CLF_KEYS:
-            par = nn.Parameter(self._view(self.head_p, name), requires_grad=True)
-            par._medvill_head = weakref.ref(self)
-            self.clf._parameters[name.split(".")[1]] = par
-            self._hplist.append(par)
-        self._head_versions = None
-        self.clf_stats = None
-        self.reset_head()
 
     def _apply(self, fn, *a, **k):
         super()._apply(fn, *a, **k)
@@ -173,13 +127,10 @@ class CXRBertForClassification(CXRBertForVQA):
     # ------------------------------------------------------------------ forward / backward
     def _encode_and_classify(self, cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok):
         """Encoder (last layer on the B [CLS] rows) + the engine's pooler + clf -> logits [B, Cp] f32 (columns C..Cp-1 unspecified)."""
-        from .data import MaskDesc
         eng = self.bert.engine
         B = int(input_txt.shape[0])
         H, C, Cp = self.bert.cfg.hidden, self.n_classes, self.Ap
-        pack = isinstance(attn_mask, MaskDesc) and eng.is16 and attn_mask.packable()
-        none = torch.arange(B, device=eng.device, dtype=torch.int32)[:0]
-        eng.encoder_forward(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, pack=pack, tail_rows=none)
+        self.encode_cls_rows(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok)
         pooled = eng.S["pooled_f"]
         W = self._view(self._shadow_of(eng.fdt), CLF_KEYS[0], padded=True)
         b = self._view(self.head_p, CLF_KEYS[1])
@@ -196,10 +147,7 @@ class CXRBertForClassification(CXRBertForVQA):
         eng = self.bert.engine
         B, C, Cp, H = ctx.B, self.n_classes, self.Ap, self.bert.cfg.hidden
         eng.zero_grad()
-        if self.head_g is None:
-            self.head_g = torch.zeros_like(self.head_p)
-        else:
-            self.head_g.zero_()
+        self._zero_head_grad()
         adt, us = eng.adt, eng.unscale_dev
         dl = eng._buf("clf_dlogits", (B, Cp), adt)
         if ctx.mode == "loss":
@@ -226,7 +174,8 @@ class CXRBertForClassification(CXRBertForVQA):
         feats, pos = self.bert._regions(input_img)
         want_grad = torch.is_grad_enabled()
         if want_grad:
-            _check_single_rank()
+            check_single_rank("CXRBertForClassification", "data-parallel fine-tuning is not supported (the head's gradients would not be "
+                              "all-reduced); fine-tune on one rank, or run inference under torch.no_grad()")
         eng = self.bert.engine
         B, C = int(input_txt.shape[0]), self.n_classes
         target = None
@@ -234,7 +183,7 @@ class CXRBertForClassification(CXRBertForVQA):
             target = torch.as_tensor(labels).to(eng.device, torch.float32).contiguous()
             if tuple(target.shape) != (B, C):
                 raise ValueError(f"labels must be the multi-hot [B, C] = [{B}, {C}], got {tuple(target.shape)}")
-        self._prepare(want_grad)
+        self._prepare(want_grad)                 # (engine state NOT restored after the call, as VQA; the report model restores it)
         params = list(self.bert._plist) + self._hplist
         return _ClfFn.apply(self, "logits" if target is None else "loss", cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok,
                             target, *params)
@@ -245,79 +194,38 @@ class CXRBertForClassification(CXRBertForVQA):
         if attn_mask.dim() not in (2, 3):
             raise NotImplementedError
         feats, pos = self.bert._regions(input_img)
-        eng = self.bert.engine
-        prev = (eng.training, eng.keep_acts)
-        try:
+        with self._engine_state("training", "keep_acts") as eng:
             self._prepare(False)
             logits = self._encode_and_classify(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok)
             probs = torch.empty(int(input_txt.shape[0]), self.n_classes, dtype=torch.float32, device=eng.device)
             ops.bce_multilabel(logits, self.n_classes, ld=self.Ap, probs=probs)
-        finally:
-            eng.training, eng.keep_acts = prev
         return probs
 
     # ------------------------------------------------------------------ state dict (MultimodalBertClf's layout)
     def state_dict(self, *a, **k):
         """CXRBERT's enc.* names (aliases included) plus clf.weight / clf.bias -- no mlm.* / itm.* (the model has neither head)."""
         out = OrderedDict((k_, v) for k_, v in self.bert.state_dict().items() if k_.startswith("enc."))
-        for name, p in zip(CLF_KEYS, self._hplist):
-            out[name] = p.detach().clone()
-        return out
+        return self._head_state(out)
 
     def load_state_dict(self, sd, strict=True):
         """This layout, or a CXRBERT pretraining state dict (enc.* / mlm.* / itm.*: the head then starts from reset_head()).  The
         reference's unused enc.clf.* and its enc.img_encoder.* are ignored."""
         head = {k_: v for k_, v in sd.items() if k_ in CLF_KEYS}
         rest = OrderedDict((k_, v) for k_, v in sd.items() if k_ not in CLF_KEYS and not k_.startswith(("enc.clf.", "enc.img_encoder.")))
-        r = self.bert.load_state_dict(rest, strict=False)
-        missing = [k_ for k_ in r.missing_keys if not k_.startswith(("mlm.", "itm."))]
-        unexpected = list(r.unexpected_keys)
-        with torch.no_grad():
-            if head:
-                for name in CLF_KEYS:
-                    if name in head:
-                        self._view(self.head_p, name).copy_(head[name].to(self.head_p.device, torch.float32))
-                    else:
-                        missing.append(name)
-            else:
-                self.reset_head()
-        self._head_versions = None
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"load_state_dict: missing {missing[:5]} unexpected {unexpected[:5]}")
-        return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
+        return self._load_state(head, rest, strict)
 
     def save_pretrained(self, save_directory):
-        os.makedirs(save_directory, exist_ok=True)
-        c = self.bert.cfg
-        cj = dict(architectures=["CXRBertForClassification"], model_type="bert", vocab_size=c.vocab_size, hidden_size=c.hidden,
-                  num_hidden_layers=c.layers, num_attention_heads=c.heads, intermediate_size=c.intermediate,
-                  max_position_embeddings=c.max_pos, type_vocab_size=c.type_vocab, layer_norm_eps=c.ln_eps, hidden_act="gelu",
-                  hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, n_classes=self.n_classes)
-        with open(os.path.join(save_directory, "config.json"), "w") as f:
-            json.dump(cj, f, indent=2)
-        torch.save({k_: v.cpu() for k_, v in self.state_dict().items()}, os.path.join(save_directory, "pytorch_model.bin"))
+        write_pretrained(save_directory, hf_config(self.bert.cfg, "CXRBertForClassification", n_classes=self.n_classes), self.state_dict())
 
     @classmethod
     def from_pretrained(cls, path_or_state_dict, config=None, args=None, n_classes=None, **kw):
-        if isinstance(path_or_state_dict, (str, os.PathLike)):
-            if config is None:
-                with open(os.path.join(path_or_state_dict, "config.json")) as f:
-                    config = json.load(f)
-            sd = torch.load(os.path.join(path_or_state_dict, "pytorch_model.bin"), map_location="cpu")
-        else:
-            sd = path_or_state_dict
-            if config is None:
-                raise ValueError("from_pretrained(state_dict): pass config= as well")
+        config, sd = read_pretrained(path_or_state_dict, config)
         if n_classes is None:
             w = sd.get(CLF_KEYS[0])
             n_classes = int(w.shape[0]) if w is not None else int(config.get("n_classes", 14) if isinstance(config, dict) else 14)
         m = cls(config, args, n_classes=n_classes, **kw)
         m.load_state_dict(sd, strict=False)
         return m
-
-    # the VQA task methods do not apply to this model
-    def _classify(self, *a, **k):
-        raise NotImplementedError
 
 
 # ---------------------------------------------------------------------------------------------------- metrics (torch, no sklearn)

@@ -15,8 +15,6 @@ user-supplied ``img_encoder`` callable maps to that tuple.
 """
 from __future__ import annotations
 
-import json
-import os
 from collections import OrderedDict
 from dataclasses import replace
 import weakref
@@ -25,6 +23,7 @@ from types import SimpleNamespace
 import torch
 import torch.nn as nn
 
+from .checkpoint import from_finetune_keys, hf_config, read_config, read_pretrained, write_pretrained
 from .engine import ALIASES, Engine, ModelConfig
 
 
@@ -135,29 +134,40 @@ class _CXRBertFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g0, g1=None):
-        model = ctx.model
-        eng = model.engine
-        # gradients a previous backward left in the flat buffer THROUGH the .grad views (no zero_grad in between, or
-        # zero_grad(set_to_none=False)): keep them, this backward adds to them like autograd would.  Decided here, when the backward starts:
-        # a zero_grad() between the loss and the backward (the reference's order, train_origin.py:129-131) changes what .grad holds
-        held = eng.flat_g.clone() if (_use_views(model) and eng.flat_g is not None and _holds_views(model)) else None
-        _CXRBertFn._backward_once(ctx, g0, g1)
-        if eng.scaler is not None:
-            # f16 gradient operands under a loss scale: this path hands gradients to torch (an external optimizer), so an
-            # overflow cannot be turned into a skipped step -- the backward is redone with a smaller scale instead (the saved
-            # activations are still there).  One host sync per try; this is the drop-in path, not the fused training step.
-            for _ in range(8):
-                eng.scaler[6:7].zero_()
-                from . import hip_ops as ops
-                ops.count_nonfinite(eng.flat_g, eng.scaler[6:7])
-                if float(eng.scaler[6]) == 0.0:
-                    break
-                s_new = max(float(eng.scaler[0]) / 16.0, 1.0)
-                eng.reset_scaler(s_new)
-                _CXRBertFn._backward_once(ctx, g0, g1)
-        if held is not None:
-            eng.flat_g.add_(held)
-        return (None,) * 9 + _hand_over_grads(model)
+        return (None,) * 9 + run_backward(ctx.model, lambda: _CXRBertFn._backward_once(ctx, g0, g1))
+
+
+def run_backward(bert, once, head=None):
+    """The backward of a whole-network autograd node: `once()` runs the engine's backward schedule into the flat gradient buffer (and
+    into `head.head_g` when the task has a task.FlatHead) -> the gradients for autograd, in Parameter order, the head's last.
+    Gradients a previous backward left in the flat buffers THROUGH the .grad views (no zero_grad in between, or
+    zero_grad(set_to_none=False)) are kept: this backward adds to them like autograd would.  Decided here, when the backward starts: a
+    zero_grad() between the loss and the backward (the reference's order, train_origin.py:129-131) changes what .grad holds.
+    f16 gradient operands under a loss scale: the gradients go to torch (an optimizer that cannot skip the step), so an overflow -- the
+    head's buffer included -- cannot become a skipped step; the backward is redone with S / 16 instead (the saved activations are still
+    there).  One host sync per try; this is the drop-in path, not the fused training step."""
+    from . import hip_ops as ops
+    eng = bert.engine
+    views = _use_views(bert)
+    held = eng.flat_g.clone() if (views and eng.flat_g is not None and _holds_views(bert)) else None
+    held_h = head.head_g.clone() if (head is not None and views and head.head_g is not None and head._head_holds_views()) else None
+    once()
+    if eng.scaler is not None:
+        for _ in range(8):
+            eng.scaler[6:7].zero_()
+            ops.count_nonfinite(eng.flat_g, eng.scaler[6:7])
+            if head is not None:
+                ops.count_nonfinite(head.head_g, eng.scaler[6:7])
+            if float(eng.scaler[6]) == 0.0:
+                break
+            eng.reset_scaler(max(float(eng.scaler[0]) / 16.0, 1.0))
+            once()
+    if held is not None:
+        eng.flat_g.add_(held)
+    if held_h is not None:
+        head.head_g.add_(held_h)
+    grads = _hand_over_grads(bert)
+    return grads if head is None else grads + head._hand_over_head(views)
 
 
 def _use_views(model):
@@ -642,27 +652,17 @@ class CXRBERT(nn.Module):
 
     def save_pretrained(self, save_directory):
         """HF layout: config.json + pytorch_model.bin (train_origin.py:254-266)."""
-        os.makedirs(save_directory, exist_ok=True)
-        c = self.cfg
-        cj = dict(architectures=["CXRBERT"], model_type="bert", vocab_size=c.vocab_size, hidden_size=c.hidden,
-                  num_hidden_layers=c.layers, num_attention_heads=c.heads, intermediate_size=c.intermediate,
-                  max_position_embeddings=c.max_pos, type_vocab_size=c.type_vocab, layer_norm_eps=c.ln_eps,
-                  hidden_act="gelu", hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1)
-        with open(os.path.join(save_directory, "config.json"), "w") as f:
-            json.dump(cj, f, indent=2)
-        torch.save({k_: v.cpu() for k_, v in self.state_dict().items()}, os.path.join(save_directory, "pytorch_model.bin"))
+        write_pretrained(save_directory, hf_config(self.cfg, "CXRBERT"), self.state_dict())
 
     @classmethod
     def from_pretrained(cls, path, state_dict=None, config=None, args=None, **kw):
         if config is None:
-            with open(os.path.join(path, "config.json")) as f:
-                config = json.load(f)
+            config = read_config(path)
         if state_dict is None:
-            state_dict = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu")
+            _, state_dict = read_pretrained(path, config)
         if not any(k_.startswith("enc.") for k_ in state_dict) and any(k_.startswith(("encoder.", "txt_embeddings.", "cls.")) for k_ in state_dict):
             # the downstream programs' fine-tune layout (finetune.py:338-339; CXRBertForReportFinetune.save_pretrained): enc. stripped,
             # mlm. -> cls. -- a pretraining-layout dict (enc.* keys) is loaded as it is
-            from .checkpoint import from_finetune_keys
             state_dict = from_finetune_keys(state_dict)
         m = cls(config, args, **kw)
         m.load_state_dict(state_dict, strict=False)

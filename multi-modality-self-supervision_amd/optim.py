@@ -17,7 +17,41 @@ from __future__ import annotations
 import torch
 
 
-class AdamW(torch.optim.Optimizer):
+class _FlatState:
+    """state_dict / load_state_dict of an optimizer over the engine's flat buffers (`_model`) and, when the Parameters of a task head
+    were passed with them, over that head's (`_task`, a task.FlatHead): the step count `_t`, the groups' hyper-parameters and the
+    moment buffers (flat_m / flat_v, head_m / head_v) on the host."""
+
+    def state_dict(self):
+        eng = self._model.engine
+        eng.wait_optimizer()
+        eng.ensure_opt()
+        sd = {"step": self._t, "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
+              "flat_m": eng.flat_m.detach().cpu(), "flat_v": eng.flat_v.detach().cpu()}
+        task = self._task
+        if task is not None and task.head_m is not None:
+            sd["head_m"], sd["head_v"] = task.head_m.detach().cpu(), task.head_v.detach().cpu()
+        return sd
+
+    def load_state_dict(self, sd):
+        eng = self._model.engine
+        eng.wait_optimizer()
+        eng.ensure_opt()
+        if tuple(sd["flat_m"].shape) != tuple(eng.flat_m.shape):
+            raise ValueError("optimizer state of a different model configuration")
+        eng.flat_m.copy_(sd["flat_m"].to(eng.device))
+        eng.flat_v.copy_(sd["flat_v"].to(eng.device))
+        task = self._task
+        if task is not None and "head_m" in sd:
+            if tuple(sd["head_m"].shape) != tuple(task.head_p.shape):
+                raise ValueError("optimizer state of a different task head")
+            task.head_m, task.head_v = sd["head_m"].to(task.head_p.device).clone(), sd["head_v"].to(task.head_p.device).clone()
+        self._t = int(sd["step"])
+        for g, s in zip(self.param_groups, sd.get("param_groups", [])):
+            g.update({k: v for k, v in s.items() if k != "params"})
+
+
+class AdamW(_FlatState, torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, overlap=False):
         """overlap=True: the update runs per parameter range on the engine's side stream and the next forward waits range by range (what the
         fused training step does: the HBM-bound update hides under the next step's first layers).  Anything ELSE that reads the Parameters on
@@ -31,13 +65,13 @@ class AdamW(torch.optim.Optimizer):
             raise ValueError("these are not the Parameters of a medvill_amd.CXRBERT: use a torch optimizer")
         own = {id(p) for p in model._plist}
         extra = [p for p in params if id(p) not in own]
-        # a medvill_amd.CXRBertForVQA's parameters: the encoder's flat buffer plus the answer classifier's own flat buffer (one more
-        # fused launch per step).  Only the classifier of THIS encoder, and all of it; any other foreign parameter is refused below
-        vqa = _vqa_of(model, extra)
-        head_ids = {id(q) for q in vqa._hplist} if vqa is not None else set()
+        # a task model's parameters (task.FlatHead): the encoder's flat buffer plus the task head's own flat buffer (one more fused
+        # launch per step).  Only the head of THIS encoder, and all of it; any other foreign parameter is refused below
+        task = _task_of(model, extra)
+        head_ids = {id(q) for q in task._hplist} if task is not None else set()
         head = [p for p in extra if id(p) in head_ids]
         if head and len({id(p) for p in head}) != len(head_ids):
-            raise ValueError("medvill_amd.optim.AdamW updates the answer classifier's whole flat buffer: pass ALL of its parameters")
+            raise ValueError("medvill_amd.optim.AdamW updates the task head's whole flat buffer: pass ALL of its parameters")
         extra = [p for p in extra if id(p) not in head_ids]
         if len({id(p) for p in params} & own) != len(own):
             raise ValueError("medvill_amd.optim.AdamW updates the model's whole flat parameter buffer: pass ALL of model.parameters() "
@@ -49,15 +83,16 @@ class AdamW(torch.optim.Optimizer):
         super().__init__([p for p in params if id(p) in own] + head,
                          dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias))
         self._model, self._t, self.overlap = model, 0, bool(overlap)
-        self._vqa = vqa if head else None
+        self._task = task if head else None
 
     @torch.no_grad()
     def step(self, closure=None):
+        from . import hip_ops as ops
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        model = self._model
+        model, task = self._model, self._task
         eng = model.engine
         grads = [p.grad for p in model._plist]
         if all(g is None for g in grads):
@@ -72,55 +107,29 @@ class AdamW(torch.optim.Optimizer):
         self._t += 1
         eng.adamw_step(self._t, lr=float(hp["lr"]), betas=tuple(hp["betas"]), eps=float(hp["eps"]), weight_decay=float(hp["weight_decay"]),
                        correct_bias=bool(hp["correct_bias"]), overlap=self.overlap)
-        if self._vqa is not None:        # the answer classifier: same hyper-parameters, same step count
-            self._vqa._adamw_head(self._t, float(hp["lr"]), tuple(hp["betas"]), float(hp["eps"]), float(hp["weight_decay"]),
-                                  bool(hp["correct_bias"]))
+        hgrads = [p.grad for p in task._hplist] if task is not None else []
+        if any(g is None for g in hgrads) and not all(g is None for g in hgrads):
+            raise RuntimeError("some classifier Parameters have a gradient and some have none: the flat update cannot skip individual tensors")
+        if hgrads and hgrads[0] is not None:        # the task head: same hyper-parameters, same step count
+            task._gather_head_grads()
+            ops.adamw_step(task.head_p, task.head_g, task.head_m, task.head_v, task.head_sh, task._n_head, float(hp["lr"]), hp["betas"][0],
+                           hp["betas"][1], float(hp["eps"]), float(hp["weight_decay"]), self._t, bool(hp["correct_bias"]), 1.0,
+                           shadow_f16=task.head_shf)
+            task._head_written()             # the kernel has written the 16-bit copies too
         # the kernel has written the 16-bit copies: until somebody else modifies a Parameter in place (version counters), forwards need not
         model._opt_versions = sum(p._version for p in model._plist)
         return loss
 
-    def state_dict(self):
-        eng = self._model.engine
-        eng.wait_optimizer()
-        eng.ensure_opt()
-        sd = {"step": self._t, "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
-              "flat_m": eng.flat_m.detach().cpu(), "flat_v": eng.flat_v.detach().cpu()}
-        vqa = self._vqa
-        if vqa is not None and vqa.head_m is not None:
-            sd["head_m"], sd["head_v"] = vqa.head_m.detach().cpu(), vqa.head_v.detach().cpu()
-        return sd
 
-    def load_state_dict(self, sd):
-        eng = self._model.engine
-        eng.wait_optimizer()
-        eng.ensure_opt()
-        if tuple(sd["flat_m"].shape) != tuple(eng.flat_m.shape):
-            raise ValueError("optimizer state of a different model configuration")
-        eng.flat_m.copy_(sd["flat_m"].to(eng.device))
-        eng.flat_v.copy_(sd["flat_v"].to(eng.device))
-        vqa = self._vqa
-        if vqa is not None and "head_m" in sd:
-            if tuple(sd["head_m"].shape) != tuple(vqa.head_p.shape):
-                raise ValueError("optimizer state of a different answer classifier")
-            vqa.head_m, vqa.head_v = sd["head_m"].to(vqa.head_p.device).clone(), sd["head_v"].to(vqa.head_p.device).clone()
-        self._t = int(sd["step"])
-        for g, s in zip(self.param_groups, sd.get("param_groups", [])):
-            g.update({k: v for k, v in s.items() if k != "params"})
-
-
-def _vqa_of(model, extra):
-    """The CXRBertForVQA whose encoder is `model` and whose classifier Parameters are among `extra` (None otherwise).  (BertAdam uses it
-    as its task hook under the name _task_of: any task module that marks its head Parameters with `_medvill_head` and carries
-    `_hplist`, `_head_keys`, `_layout`, `_unreached` and the head_* buffers is found the same way; today that is the VQA model.)"""
+def _task_of(model, extra):
+    """The task model (task.FlatHead: CXRBertForVQA, CXRBertForClassification) whose encoder is `model` and whose head Parameters,
+    marked with `_medvill_head`, are among `extra` (None otherwise)."""
     for p in extra:
         ref = getattr(p, "_medvill_head", None)
-        vqa = ref() if ref is not None else None
-        if vqa is not None and vqa.bert is model:
-            return vqa
+        task = ref() if ref is not None else None
+        if task is not None and task.bert is model:
+            return task
     return None
-
-
-_task_of = _vqa_of          # BertAdam's name for the hook: CXRBertForVQA and CXRBertForClassification are both found this way
 
 
 # ======================================================================================================================== BertAdam
@@ -169,7 +178,7 @@ class _Tables:
         self.sq = torch.zeros(self.tensors.shape[0], dtype=torch.float32, device=device)
 
 
-class BertAdam(torch.optim.Optimizer):
+class BertAdam(_FlatState, torch.optim.Optimizer):
     """The reference's fine-tuning optimizer (pytorch_pretrained_bert/optimization.py:57-182) on the flat buffers: per TENSOR gradient-norm
     clipping, weight decay on the tensors of the groups that ask for it, a warm-up schedule evaluated on `step` BEFORE its increment (so
     the first step under warm-up moves nothing but updates the moments) and no bias correction.  Two launches per flat buffer
@@ -344,49 +353,13 @@ class BertAdam(torch.optim.Optimizer):
         eng.shadow_dirty = False
         eng.refresh_w2t()
         if task is not None:
-            if task.head_g is None:
-                task.head_g = torch.zeros_like(task.head_p)
-            for name, g in zip(task._head_keys, hgrads):
-                gv = task._view(task.head_g, name)
-                if g.data_ptr() != gv.data_ptr():
-                    gv.copy_(g)
-            if task.head_m is None:
-                task.head_m, task.head_v = torch.zeros_like(task.head_p), torch.zeros_like(task.head_p)
+            task._gather_head_grads()
             if clip:
                 ops.tensor_sqnorms(task.head_g, htab.tensors, htab.chunks, htab.partials, htab.sq)
             ops.bertadam_step(task.head_p, task.head_g, task.head_m, task.head_v, htab.tensors, htab.chunks, htab.sq if clip else None,
                               shadow=task.head_sh, shadow_f16=task.head_shf, **kw)
-            task._head_versions = sum(p._version for p in task._hplist)      # the kernel has written the 16-bit copies too
+            task._head_written()             # the kernel has written the 16-bit copies too
         self._t += 1
         # the kernel has written the 16-bit copies: until somebody else modifies a Parameter in place (version counters), forwards need not
         model._opt_versions = sum(p._version for p in model._plist)
         return loss
-
-    def state_dict(self):
-        eng = self._model.engine
-        eng.wait_optimizer()
-        eng.ensure_opt()
-        sd = {"step": self._t, "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
-              "flat_m": eng.flat_m.detach().cpu(), "flat_v": eng.flat_v.detach().cpu()}
-        task = self._task
-        if task is not None and task.head_m is not None:
-            sd["head_m"], sd["head_v"] = task.head_m.detach().cpu(), task.head_v.detach().cpu()
-        return sd
-
-    def load_state_dict(self, sd):
-        eng = self._model.engine
-        eng.wait_optimizer()
-        eng.ensure_opt()
-        if tuple(sd["flat_m"].shape) != tuple(eng.flat_m.shape):
-            raise ValueError("optimizer state of a different model configuration")
-        eng.flat_m.copy_(sd["flat_m"].to(eng.device))
-        eng.flat_v.copy_(sd["flat_v"].to(eng.device))
-        task = self._task
-        if task is not None and "head_m" in sd:
-            if tuple(sd["head_m"].shape) != tuple(task.head_p.shape):
-                raise ValueError("optimizer state of a different task head")
-            task.head_m, task.head_v = sd["head_m"].to(task.head_p.device).clone(), sd["head_v"].to(task.head_p.device).clone()
-        self._t = int(sd["step"])
-        for g, s in zip(self.param_groups, sd.get("param_groups", [])):
-            g.update({k: v for k, v in s.items() if k != "params"})
-

@@ -18,17 +18,15 @@ reference's `grad is None`.  DESIGN.md "8e. Report fine-tuning".
 """
 from __future__ import annotations
 
-import json
-import os
 import weakref
 from types import SimpleNamespace
 
 import torch
-import torch.nn as nn
 
 from . import hip_ops as ops
-from .checkpoint import from_finetune_keys, to_finetune_keys
-from .cxrbert import CXRBERT, _hand_over_grads, _holds_views, _use_views
+from .checkpoint import from_finetune_keys, hf_config, read_pretrained, to_finetune_keys, write_pretrained
+from .cxrbert import run_backward
+from .task import TaskModel, check_single_rank
 
 
 def keep_count(B: int, drop_worst_ratio: float) -> int:
@@ -79,13 +77,6 @@ def build_plan(masked_pos, masked_lm_labels, masked_weights, L: int, V: int, val
                 labels=t[order].to(torch.int32).contiguous(), weights=wt[order].contiguous(), sample=b_idx[order].to(torch.int32).contiguous())
 
 
-def _check_single_rank():
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise RuntimeError("CXRBertForReportFinetune: data-parallel fine-tuning is not supported (drop-worst selects over the whole "
-                           "batch and the gradients would not be all-reduced); fine-tune on one rank, or evaluate under torch.no_grad()")
-
-
 class _ReportFn(torch.autograd.Function):
     """Encoder (last layer on the distinct consumed rows) + MLM head + the objective as one autograd node."""
 
@@ -98,27 +89,10 @@ class _ReportFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         model = ctx.model
-        bert = model.bert
-        eng = bert.engine
-        # gradients an earlier backward left in the flat buffer THROUGH the .grad views: kept and added to, like autograd would
-        held = eng.flat_g.clone() if (_use_views(bert) and eng.flat_g is not None and _holds_views(bert)) else None
-        model._backward_once(ctx, g)
-        if eng.scaler is not None:
-            # f16 gradient operands under a loss scale (as _CXRBertFn.backward): an overflow is redone with a smaller scale, because the
-            # gradients go to an optimizer that cannot skip the step
-            for _ in range(8):
-                eng.scaler[6:7].zero_()
-                ops.count_nonfinite(eng.flat_g, eng.scaler[6:7])
-                if float(eng.scaler[6]) == 0.0:
-                    break
-                eng.reset_scaler(max(float(eng.scaler[0]) / 16.0, 1.0))
-                model._backward_once(ctx, g)
-        if held is not None:
-            eng.flat_g.add_(held)
-        return (None,) * 10 + _hand_over_grads(bert)
+        return (None,) * 10 + run_backward(model.bert, lambda: model._backward_once(ctx, g))
 
 
-class CXRBertForReportFinetune(nn.Module):
+class CXRBertForReportFinetune(TaskModel):
     """`BertForPreTrainingLossMask(config, args, tasks='report_generation')` with this package's CXRBERT input convention:
         forward(cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, masked_lm_labels=, masked_pos=, masked_weights=,
                 drop_worst_ratio=0.0) -> (masked_lm_loss, dummy zero [1])                               (model.py:1054)
@@ -132,11 +106,7 @@ class CXRBertForReportFinetune(nn.Module):
     _unreached = ("itm.", "enc.pooler.")
 
     def __init__(self, config, args=None, label_smoothing=None, **kw):
-        super().__init__()
-        self.bert = CXRBERT(config, args, **kw)
-        self._adopt(config, label_smoothing)
-
-    def _adopt(self, config, label_smoothing):
+        super().__init__(config, args, **kw)
         if label_smoothing is None:
             label_smoothing = (config.get("label_smoothing") if isinstance(config, dict) else getattr(config, "label_smoothing", None)) or 0.0
         label_smoothing = float(label_smoothing)
@@ -150,20 +120,11 @@ class CXRBertForReportFinetune(nn.Module):
         self.bert._headless_task = weakref.ref(self)
 
     # ------------------------------------------------------------------ forward
-    def _prepare(self, want_grad):
-        bert = self.bert
-        eng = bert.engine
-        if not bert.__dict__.pop("_shadow_fresh", False):
-            eng.shadow_dirty = eng.shadow_dirty or bert._params_dirty()
-        eng.training = self.training             # dropout only in train mode
-        eng.keep_acts = bool(want_grad)          # under torch.no_grad() nothing is saved for a backward
-
     def _forward_loss(self, plan, k, cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok):
-        from .data import MaskDesc
         eng = self.bert.engine
         dev = eng.device
         B, U = plan["B"], plan["U"]
-        pack = isinstance(attn_mask, MaskDesc) and eng.is16 and attn_mask.packable()
+        pack = self._pack(attn_mask)
         d = {k_: plan[k_].to(dev) for k_ in ("rows", "row_ptr", "labels", "weights", "sample")}
         eng.encoder_forward(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, pack=pack, tail_rows=d["rows"])
         S, V = eng.S, self.bert.cfg.vocab_size
@@ -200,7 +161,6 @@ class CXRBertForReportFinetune(nn.Module):
 
     def forward(self, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, masked_lm_labels=None, masked_pos=None,
                 masked_weights=None, drop_worst_ratio=0.0):
-        from .data import MaskDesc
         if masked_lm_labels is None or masked_pos is None or masked_weights is None:
             raise ValueError("CXRBertForReportFinetune.forward needs masked_lm_labels, masked_pos and masked_weights (model.py:1043-1053); "
                              "decode with CXRBertForGeneration / CXRBERT.generate")
@@ -209,27 +169,24 @@ class CXRBertForReportFinetune(nn.Module):
         feats, pos = self.bert._regions(input_img)
         want_grad = torch.is_grad_enabled()
         if want_grad:
-            _check_single_rank()
-        eng = self.bert.engine
+            check_single_rank("CXRBertForReportFinetune", "data-parallel fine-tuning is not supported (drop-worst selects over the whole "
+                              "batch and the gradients would not be all-reduced); fine-tune on one rank, or evaluate under torch.no_grad()")
         B, N = int(input_txt.shape[0]), int(feats.shape[1])
         Lq = N + int(input_txt.shape[1]) + 2
         trio = (masked_pos, masked_lm_labels, masked_weights)
         if all(torch.is_tensor(t) and t.is_cuda for t in trio) and len({tuple(t.shape) for t in trio}) == 1:
             host = torch.stack([t.to(torch.float64) for t in trio]).cpu()      # one read-back of the three small arrays
             trio = (host[0].to(torch.int64), host[1].to(torch.int64), host[2].to(torch.float32))
-        pack = isinstance(attn_mask, MaskDesc) and eng.is16 and attn_mask.packable()
+        pack = self._pack(attn_mask)
         plan = build_plan(*trio, L=Lq, V=self.bert.cfg.vocab_size, valid_len=attn_mask.host_desc()[:, 2] if pack else None)
         if plan["B"] != B:
             raise ValueError(f"masked_pos holds {plan['B']} samples, the batch {B}")
         k = keep_count(B, drop_worst_ratio)
         if not 0 <= k <= B:
             raise ValueError(f"drop_worst_ratio {drop_worst_ratio} keeps {k} of {B} samples")
-        prev = (eng.training, eng.keep_acts)
-        try:
+        with self._engine_state("training", "keep_acts"):       # restored after the call (the VQA / classification forwards leave it set)
             self._prepare(want_grad)
             loss = _ReportFn.apply(self, plan, k, cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, *self.bert._plist)
-        finally:                # sticky engine state: a later direct Engine user must find what it left
-            eng.training, eng.keep_acts = prev
         return loss, loss.new_zeros(1)           # (masked_lm_loss, dummy_value), model.py:1054
 
     def generate(self, cls_tok, input_img, sep_tok, **kw):
@@ -256,28 +213,13 @@ class CXRBertForReportFinetune(nn.Module):
     def save_pretrained(self, save_directory):
         """config.json + pytorch_model.bin in the fine-tune layout; CXRBERT.from_pretrained / CXRBertForGeneration.from_pretrained
         read it back."""
-        os.makedirs(save_directory, exist_ok=True)
-        c = self.bert.cfg
-        cj = dict(architectures=["CXRBertForReportFinetune"], model_type="bert", vocab_size=c.vocab_size, hidden_size=c.hidden,
-                  num_hidden_layers=c.layers, num_attention_heads=c.heads, intermediate_size=c.intermediate,
-                  max_position_embeddings=c.max_pos, type_vocab_size=c.type_vocab, layer_norm_eps=c.ln_eps, hidden_act="gelu",
-                  hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, label_smoothing=self.label_smoothing)
-        with open(os.path.join(save_directory, "config.json"), "w") as f:
-            json.dump(cj, f, indent=2)
-        torch.save({k_: v.cpu() for k_, v in self.state_dict().items()}, os.path.join(save_directory, "pytorch_model.bin"))
+        write_pretrained(save_directory, hf_config(self.bert.cfg, "CXRBertForReportFinetune", label_smoothing=self.label_smoothing),
+                         self.state_dict())
 
     @classmethod
     def from_pretrained(cls, path_or_state_dict, config=None, args=None, label_smoothing=None, **kw):
         """A checkpoint directory (CXRBERT.save_pretrained or save_pretrained above) or a state dict (then `config` is required)."""
-        if isinstance(path_or_state_dict, (str, os.PathLike)):
-            if config is None:
-                with open(os.path.join(path_or_state_dict, "config.json")) as f:
-                    config = json.load(f)
-            sd = torch.load(os.path.join(path_or_state_dict, "pytorch_model.bin"), map_location="cpu")
-        else:
-            sd = path_or_state_dict
-            if config is None:
-                raise ValueError("from_pretrained(state_dict): pass config= as well")
+        config, sd = read_pretrained(path_or_state_dict, config)
         m = cls(config, args, label_smoothing=label_smoothing, **kw)
         m.load_state_dict(sd, strict=False)
         return m

@@ -3,21 +3,16 @@ top of CXRBERT.enc + .itm with 1-D attention masks (the `attn_mask.dim() == 2` b
 Encoder-only inference / fine-tuning through the same HIP kernels."""
 from __future__ import annotations
 
-import json
-import os
-
 import torch
 import torch.nn as nn
 
 from . import hip_ops as ops
-from .cxrbert import CXRBERT, _hand_over_grads, _holds_views, _use_views
+from .checkpoint import hf_config, write_pretrained
+from .cxrbert import CXRBERT, run_backward
+from .task import TaskModel, check_single_rank
 
-
-def _check_single_rank():
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise RuntimeError("CXRBertForRetrieval: data-parallel fine-tuning through forward(labels=) / fit_step is not supported (single "
-                           "rank, as classification); fine-tune on one rank, or run evaluation under torch.no_grad()")
+_SINGLE_RANK = ("CXRBertForRetrieval", "data-parallel fine-tuning through forward(labels=) / fit_step is not supported (single "
+                "rank, as classification); fine-tune on one rank, or run evaluation under torch.no_grad()")
 
 
 # ---------------------------------------------------------------------------------------------------- host side of evaluate()
@@ -81,27 +76,12 @@ class _RetLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         model = ctx.model
-        bert = model.bert
-        eng = bert.engine
-        held = eng.flat_g.clone() if (_use_views(bert) and eng.flat_g is not None and _holds_views(bert)) else None
-        model._loss_backward(ctx.logits, ctx.labels, ctx.B, g)
-        if eng.scaler is not None:               # f16 gradients handed to torch: an overflow is redone with S / 16 (as _CXRBertFn)
-            for _ in range(8):
-                eng.scaler[6:7].zero_()
-                ops.count_nonfinite(eng.flat_g, eng.scaler[6:7])
-                if float(eng.scaler[6]) == 0.0:
-                    break
-                eng.reset_scaler(max(float(eng.scaler[0]) / 16.0, 1.0))
-                model._loss_backward(ctx.logits, ctx.labels, ctx.B, g)
-        if held is not None:
-            eng.flat_g.add_(held)
-        return (None,) * 9 + _hand_over_grads(bert)
+        return (None,) * 9 + run_backward(model.bert, lambda: model._loss_backward(ctx.logits, ctx.labels, ctx.B, g))
 
 
-class CXRBertForRetrieval(nn.Module):
+class CXRBertForRetrieval(TaskModel):
     def __init__(self, config, args=None, **kw):
-        super().__init__()
-        self.bert = CXRBERT(config, args, **kw)
+        super().__init__(config, args, **kw)
         self.enc, self.itm = self.bert.enc, self.bert.itm
 
     @classmethod
@@ -131,7 +111,7 @@ class CXRBertForRetrieval(nn.Module):
         feats, pos = bert._regions(input_img)
         self._want_grad = torch.is_grad_enabled()
         if self._want_grad:
-            _check_single_rank()
+            check_single_rank(*_SINGLE_RANK)
         return _RetLossFn.apply(self, cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, lab, *bert._plist)
 
     # ------------------------------------------------------------------ fused loss
@@ -141,22 +121,13 @@ class CXRBertForRetrieval(nn.Module):
     def _logits_cls_rows(self, cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok):
         """Encoder (packed where the mask allows it; last layer's per-row work on the B [CLS] rows only) + pooler + ITM head ->
         the engine's f32 [B, 2] logit buffer."""
-        from .data import MaskDesc
-        eng = self.bert.engine
-        B = int(input_txt.shape[0])
-        pack = isinstance(attn_mask, MaskDesc) and eng.is16 and attn_mask.packable()
-        none = torch.arange(B, device=eng.device, dtype=torch.int32)[:0]
-        eng.encoder_forward(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, pack=pack, tail_rows=none)
-        return eng._itm_forward()
+        self.encode_cls_rows(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok)
+        return self.bert.engine._itm_forward()
 
     def _loss_forward(self, cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, labels):
-        bert = self.bert
-        eng = bert.engine
+        eng = self.bert.engine
         B = int(input_txt.shape[0])
-        if not bert.__dict__.pop("_shadow_fresh", False):
-            eng.shadow_dirty = eng.shadow_dirty or bert._params_dirty()
-        eng.training = bool(self.training)
-        eng.keep_acts = bool(getattr(self, "_want_grad", True))
+        self._prepare(getattr(self, "_want_grad", True))       # (set by forward / fit_step; the engine state stays as this call set it)
         logits = self._logits_cls_rows(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok)
         st = torch.zeros(3, dtype=torch.float32, device=eng.device)
         ops.ce_fwd_bwd(logits, 2, labels, B, 2, st)
@@ -186,7 +157,7 @@ class CXRBertForRetrieval(nn.Module):
         selects the sampler's random words; `draws` overrides them, see hip_ops.pair_negatives).  f16 gradients: an overflowed step is
         skipped and the loss scale backs off on the device, as in TrainStep.  Returns the step's mean loss as a device scalar; nothing
         is read back except the 2B mask descriptors (the packed-row plan needs the row count on the host)."""
-        _check_single_rank()
+        check_single_rank(*_SINGLE_RANK)
         eng = self.bert.engine
         n = bank.n_texts
         if n != bank.n_images or n < 2:
@@ -233,17 +204,14 @@ class CXRBertForRetrieval(nn.Module):
         lab = lab.to(dev, torch.int32).contiguous()
         logits_all = torch.empty((n_pairs, 2), dtype=torch.float32, device=dev)
         ce = torch.zeros((len(plan), 3), dtype=torch.float32, device=dev)
-        prev = (eng.training, eng.keep_acts, eng.drop_counter)
         eng.shadow_dirty = eng.shadow_dirty or self.bert._params_dirty()
-        try:
+        with self._engine_state("training", "keep_acts", "drop_counter"):      # (the dropout counter too: a run of evaluation forwards)
             eng.training, eng.keep_acts = False, False
             for b, (s, e) in enumerate(plan):
                 cls_tok, input_txt, desc, segment, (feats, pos), sep_tok = bank.assemble(pairs[s:e])
                 logits = self._logits_cls_rows(cls_tok, input_txt, desc, segment, feats, pos, sep_tok)
                 logits_all[s:e].copy_(logits)
                 ops.ce_fwd_bwd(logits, 2, lab[s:e], e - s, 2, ce[b])
-        finally:                    # sticky engine state: a later direct Engine user must find what it left
-            eng.training, eng.keep_acts, eng.drop_counter = prev
         p, pos_, rank, counters = ops.rank_groups(logits_all, lab, group_size, ks)
         # the one read-back: counters | per-batch loss sums (f32 bit patterns) | pos | labels
         host = torch.cat([counters, ce[:, 0].contiguous().view(torch.int32).to(torch.int64), pos_.to(torch.int64), lab.to(torch.int64)]).cpu()
@@ -259,33 +227,20 @@ class CXRBertForRetrieval(nn.Module):
     def save_pretrained(self, save_directory):
         """config.json + pytorch_model.bin under the reference model's key names (its modules are `enc` and `itm`,
         Downstream_task/Retrieval/retrieval.py:24-25); from_pretrained -- here and CXRBERT's -- loads it back."""
-        os.makedirs(save_directory, exist_ok=True)
-        c = self.bert.cfg
-        cj = dict(architectures=["CXRBertForRetrieval"], model_type="bert", vocab_size=c.vocab_size, hidden_size=c.hidden,
-                  num_hidden_layers=c.layers, num_attention_heads=c.heads, intermediate_size=c.intermediate,
-                  max_position_embeddings=c.max_pos, type_vocab_size=c.type_vocab, layer_norm_eps=c.ln_eps, hidden_act="gelu",
-                  hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1)
-        with open(os.path.join(save_directory, "config.json"), "w") as f:
-            json.dump(cj, f, indent=2)
-        sd = {k: v.cpu() for k, v in self.bert.state_dict().items() if k.startswith(("enc.", "itm."))}
-        torch.save(sd, os.path.join(save_directory, "pytorch_model.bin"))
+        sd = {k: v for k, v in self.bert.state_dict().items() if k.startswith(("enc.", "itm."))}
+        write_pretrained(save_directory, hf_config(self.bert.cfg, "CXRBertForRetrieval"), sd)
 
     @torch.no_grad()
     def score(self, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok):
         """P(aligned) per pair, as full_dset_retrieval.py:461-510 ranks candidates.  When `attn_mask` is a
         `data.MaskDesc` of a family whose padding is invisible (the retrieval scripts' 1-D masks are), the encoder runs
         on the valid rows only (inference form of the padding removal)."""
-        from .data import MaskDesc
-        eng = self.bert.engine
-        if isinstance(attn_mask, MaskDesc) and eng.is16 and attn_mask.packable():
+        if self._pack(attn_mask):
             feats, pos = self.bert._regions(input_img)
-            prev = (eng.training, eng.keep_acts)
-            eng.training, eng.keep_acts = False, False
-            try:
+            with self._engine_state("training", "keep_acts") as eng:
+                eng.training, eng.keep_acts = False, False
                 eng.encoder_forward(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, pack=True)
                 logits = eng._itm_forward().clone()
-            finally:                # sticky engine state: a later direct Engine user must find what it left
-                eng.training, eng.keep_acts = prev
         else:
             logits = self.forward(cls_tok, input_txt, attn_mask, segment, input_img, sep_tok)
         return torch.softmax(logits.float(), dim=-1)[:, 1]

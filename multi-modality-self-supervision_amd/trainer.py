@@ -15,6 +15,7 @@ import os
 import torch
 
 from . import data as D
+from .checkpoint import WEIGHTS_NAME
 from .cxrbert import CXRBERT, model_config_from
 from .dist import GradAllReducer
 
@@ -506,7 +507,7 @@ def resolve_bert_model(args, name):
     sd = getattr(args, "init_state_dict", None)
     path = getattr(args, "init_checkpoint", None) or (name if os.path.isdir(str(name)) else None)
     if sd is None and path is not None:
-        f = os.path.join(path, "pytorch_model.bin") if os.path.isdir(path) else path
+        f = os.path.join(path, WEIGHTS_NAME) if os.path.isdir(path) else path
         sd = torch.load(f, map_location="cpu")
         cj = os.path.join(os.path.dirname(f), "config.json")
         if config is None and os.path.exists(cj):

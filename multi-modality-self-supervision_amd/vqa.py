@@ -15,19 +15,16 @@ medvill_amd.optim.AdamW / BertAdam update with one more fused launch.  Arithmeti
 """
 from __future__ import annotations
 
-import json
-import os
-import weakref
 from collections import OrderedDict
-from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
 from . import hip_ops as ops
-from ._lib import EPI_BIAS, EPI_BIAS_RELU, MV_F16, MV_F32
-from .checkpoint import from_finetune_keys, to_finetune_keys
-from .cxrbert import CXRBERT, _hand_over_grads, _holds_views, _use_views
+from ._lib import EPI_BIAS, EPI_BIAS_RELU
+from .checkpoint import from_finetune_keys, hf_config, read_pretrained, to_finetune_keys, write_pretrained
+from .cxrbert import run_backward
+from .task import FlatHead, check_single_rank
 
 N_ANSWERS = 458          # model.py:942
 HEAD_KEYS = ("ans_classifier.0.weight", "ans_classifier.0.bias", "ans_classifier.2.weight", "ans_classifier.2.bias")
@@ -45,13 +42,6 @@ def head_layout(H: int, A: int):
         lay[name] = (off, shape)
         off += (n + 63) // 64 * 64
     return lay, off, Ap
-
-
-def _check_single_rank():
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise RuntimeError("CXRBertForVQA: data-parallel VQA fine-tuning is not supported (the classifier's gradients would not be "
-                           "all-reduced); fine-tune on one rank, or run inference under torch.no_grad()")
 
 
 class _VQAFn(torch.autograd.Function):
@@ -77,32 +67,10 @@ class _VQAFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         model = ctx.model
-        bert = model.bert
-        eng = bert.engine
-        # gradients an earlier backward left in the flat buffers THROUGH the .grad views: kept and added to, like autograd would
-        views = _use_views(bert)
-        held = eng.flat_g.clone() if (views and eng.flat_g is not None and _holds_views(bert)) else None
-        held_h = model.head_g.clone() if (views and model.head_g is not None and model._head_holds_views()) else None
-        model._backward_once(ctx, g)
-        if eng.scaler is not None:
-            # f16 gradient operands under a loss scale (as _CXRBertFn.backward): an overflow -- the classifier's gradients included -- is
-            # redone with a smaller scale, because the gradients go to an optimizer that cannot skip the step
-            for _ in range(8):
-                eng.scaler[6:7].zero_()
-                ops.count_nonfinite(eng.flat_g, eng.scaler[6:7])
-                ops.count_nonfinite(model.head_g, eng.scaler[6:7])
-                if float(eng.scaler[6]) == 0.0:
-                    break
-                eng.reset_scaler(max(float(eng.scaler[0]) / 16.0, 1.0))
-                model._backward_once(ctx, g)
-        if held is not None:
-            eng.flat_g.add_(held)
-        if held_h is not None:
-            model.head_g.add_(held_h)
-        return (None,) * 11 + _hand_over_grads(bert) + model._hand_over_head(views)
+        return (None,) * 11 + run_backward(model.bert, lambda: model._backward_once(ctx, g), head=model)
 
 
-class CXRBertForVQA(nn.Module):
+class CXRBertForVQA(FlatHead):
     """`BertForPreTrainingLossMask(config, args, tasks='vqa')` with this package's CXRBERT input convention:
         forward(cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, ans_labels=None, ans_type=None, vqa_inference=False)
           ans_labels (soft targets f32 [B, A], data_loader.py:255-272) -> (dummy zero [1], mean BCE loss); model.vqa_stats =
@@ -110,7 +78,8 @@ class CXRBertForVQA(nn.Module):
               model.vqa_pred = argmax over all answers (int64 [B])
           vqa_inference=True -> ans_idx int64 [B] = argmax(classifier([CLS] (.) [SEP])[:, 1:]) + 1   (model.py:979-983)
           neither -> differentiable logits [B, A] of the [CLS] row
-    .bert is the CXRBERT; .ans_classifier the Sequential(Linear, ReLU, Linear) whose Parameters are views of the classifier's flat buffer.
+    .bert is the CXRBERT; .ans_classifier the Sequential(Linear, ReLU, Linear) whose Parameters are views of the classifier's flat buffer
+    (task.FlatHead).
     `attn_mask` may be a materialised mask or data.MaskDesc descriptors (16-bit: the encoder then runs on the valid rows only)."""
 
     # medvill_amd.optim.BertAdam: the classifier's tensors, and the encoder tensors the VQA graph never reaches (`grad is None` in the
@@ -120,93 +89,13 @@ class CXRBertForVQA(nn.Module):
     _unreached = ("mlm.", "itm.", "enc.pooler.")
 
     def __init__(self, config, args=None, n_answers=N_ANSWERS, **kw):
-        super().__init__()
-        self.bert = CXRBERT(config, args, **kw)
-        self._init_head(int(n_answers))
-
-    def _init_head(self, A):
-        eng = self.bert.engine
-        H = self.bert.cfg.hidden
+        super().__init__(config, args, **kw)
+        H, A = self.bert.cfg.hidden, int(n_answers)
         self.n_answers = A
-        self._layout, self._n_head, self.Ap = head_layout(H, A)
-        dev = eng.device
-        self.head_p = torch.zeros(self._n_head, dtype=torch.float32, device=dev)
-        self.head_g = self.head_m = self.head_v = None
-        # 16-bit copies in the encodings the engine uses (the same rule as Engine.shadow / shadow_f)
-        self.head_sh = torch.zeros(self._n_head, dtype=torch.bfloat16, device=dev) if eng.shadow is not None else None
-        self.head_shf = torch.zeros(self._n_head, dtype=torch.float16, device=dev) if eng.shadow_f is not None else None
         self.ans_classifier = nn.Sequential(nn.Linear(H, 2 * H), nn.ReLU(), nn.Linear(2 * H, A))
-        self._hplist = []
-        for name in self._head_keys:
-            idx, leaf = name.split(".")[1:]
-            par = nn.Parameter(self._view(self.head_p, name), requires_grad=True)
-            par._medvill_head = weakref.ref(self)          # medvill_amd.optim.AdamW finds the classifier's flat buffers through it
-            self.ans_classifier[int(idx)]._parameters[leaf] = par
-            self._hplist.append(par)
-        self._head_versions = None
         self._acts = None
         self.vqa_stats = self.vqa_pred = None
-        self.reset_head()
-
-    # ------------------------------------------------------------------ classifier storage
-    def _view(self, buf, name, padded=False):
-        off, shape = self._layout[name]
-        if padded and name == self._padded_key:
-            shape = (self.Ap, shape[1])
-        n = 1
-        for s in shape:
-            n *= s
-        return buf[off:off + n].view(shape)
-
-    def _shadow_of(self, dt):
-        return self.head_p if dt == MV_F32 else (self.head_shf if dt == MV_F16 else self.head_sh)
-
-    def _rebind(self):
-        for name, par in zip(self._head_keys, self._hplist):
-            par.data = self._view(self.head_p, name)
-        if self.head_g is not None:
-            for name, par in zip(self._head_keys, self._hplist):
-                if par.grad is not None and par.grad.device != self.head_g.device:
-                    par.grad = None
-
-    def _apply(self, fn, *a, **k):
-        # .to(device) / .cuda(): the encoder moves its flat buffers (CXRBERT._apply), the classifier its own; the Parameters stay views
-        self.bert._apply(fn, *a, **k)
-        dev = self.bert.engine.device
-        for k_ in ("head_p", "head_g", "head_m", "head_v", "head_sh", "head_shf"):
-            t = getattr(self, k_)
-            if t is not None:
-                setattr(self, k_, t.to(dev))
-        self._head_versions = None
-        self._rebind()
-        return self
-
-    def _head_dirty(self):
-        v = self._head_versions
-        return v is None or v != sum(p._version for p in self._hplist)
-
-    def _sync_head(self):
-        """16-bit copies of the classifier from its fp32 master (after an outside optimizer or a load changed the Parameters)."""
-        for sh in (self.head_sh, self.head_shf):
-            if sh is not None:
-                ops.cast(self.head_p, sh, self._n_head)
-        self._head_versions = sum(p._version for p in self._hplist)
-
-    def _head_holds_views(self):
-        return any(p.grad is not None and p.grad.data_ptr() == self._view(self.head_g, n).data_ptr() for n, p in zip(self._head_keys, self._hplist))
-
-    def _hand_over_head(self, views):
-        """The classifier's gradients -> torch, by the rule of cxrbert._hand_over_grads (views of the flat gradient unless a hook or a
-        process group asks for copies)."""
-        out = []
-        for name, p in zip(self._head_keys, self._hplist):
-            g = self._view(self.head_g, name)
-            if views and (p.grad is None or p.grad.data_ptr() == g.data_ptr()):
-                p.grad = g
-                out.append(None)
-            else:
-                out.append(g.clone())
-        return tuple(out)
+        self._init_head(head_layout(H, A))
 
     @torch.no_grad()
     def reset_head(self, seed: int | None = None):
@@ -222,39 +111,25 @@ class CXRBertForVQA(nn.Module):
         self._head_versions = None
 
     # ------------------------------------------------------------------ forward
-    def _prepare(self, want_grad):
-        bert = self.bert
-        eng = bert.engine
-        # Parameters stepped by an outside optimizer (or loaded): refresh the 16-bit copies -- unless medvill_amd.optim.AdamW, whose
-        # kernels write them, was the last to touch them (version counters, as CXRBERT's forward)
-        if not bert.__dict__.pop("_shadow_fresh", False):
-            eng.shadow_dirty = eng.shadow_dirty or bert._params_dirty()
-        if eng.is16 and self._head_dirty():
-            self._sync_head()
-        eng.training = self.training             # encoder dropout only in train mode; the classifier has none
-        eng.keep_acts = bool(want_grad)          # under torch.no_grad() nothing is saved for a backward
-
     def _encode_and_classify(self, cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, infer):
         """Encoder (last layer on the consumed rows) + classifier -> logits [B, Ap] f32 (columns A..Ap-1 unspecified).
         Training vector: the [CLS] row (model.py:1021); inference: [CLS] (.) the image [SEP] row N+1 (model.py:980)."""
-        from .data import MaskDesc
         eng = self.bert.engine
-        dev = eng.device
         B, N = int(input_txt.shape[0]), int(feats.shape[1])
-        Lq = N + int(input_txt.shape[1]) + 2
-        pack = isinstance(attn_mask, MaskDesc) and eng.is16 and attn_mask.packable()
-        ar = torch.arange(B, device=dev, dtype=torch.int32)
+        H = self.bert.cfg.hidden
         # tail_rows: none for training (the compact final state is the B [CLS] rows); the image [SEP] rows for inference (then
         # [SEP rows | CLS rows])
-        tail = ar * Lq + (N + 1) if infer else ar[:0]
-        eng.encoder_forward(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, pack=pack, tail_rows=tail)
-        S, H = eng.S, self.bert.cfg.hidden
         if infer:
+            ar = torch.arange(B, device=eng.device, dtype=torch.int32)
+            eng.encoder_forward(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, pack=self._pack(attn_mask),
+                                tail_rows=ar * (N + int(input_txt.shape[1]) + 2) + (N + 1))
+            S = eng.S
             x = eng._buf("vqa_emb", (B, H), eng.fadt)
             ops.rows_mul(S["hidden_f"], ar + B, S["hidden_f"], ar, x, R=B, H=H)
             xb = None
         else:
-            x, xb = S["hidden_f"][:B], S["hidden"][:B]
+            self.encode_cls_rows(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok)
+            x, xb = eng.S["hidden_f"][:B], eng.S["hidden"][:B]
         return self._classify(x, xb, B)
 
     def _classify(self, x, xb, B):
@@ -289,10 +164,7 @@ class CXRBertForVQA(nn.Module):
         B, A, Ap, H = ctx.B, self.n_answers, self.Ap, bert.cfg.hidden
         acts = ctx.acts
         eng.zero_grad()
-        if self.head_g is None:
-            self.head_g = torch.zeros_like(self.head_p)
-        else:
-            self.head_g.zero_()
+        self._zero_head_grad()
         adt, us = eng.adt, eng.unscale_dev
         dl = eng._buf("vqa_dlogits", (B, Ap), adt)
         if ctx.mode == "loss":
@@ -331,7 +203,8 @@ class CXRBertForVQA(nn.Module):
             return self.predict(cls_tok, input_txt, attn_mask, segment, (feats, pos), sep_tok)
         want_grad = torch.is_grad_enabled()
         if want_grad:
-            _check_single_rank()
+            check_single_rank("CXRBertForVQA", "data-parallel VQA fine-tuning is not supported (the classifier's gradients would not be "
+                              "all-reduced); fine-tune on one rank, or run inference under torch.no_grad()")
         eng = self.bert.engine
         B, A = int(input_txt.shape[0]), self.n_answers
         target = at = None
@@ -343,7 +216,7 @@ class CXRBertForVQA(nn.Module):
                 at = torch.as_tensor(ans_type).to(eng.device, torch.int32).reshape(-1).contiguous()
                 if at.numel() != B:
                     raise ValueError("ans_type must hold one entry per sample")
-        self._prepare(want_grad)
+        self._prepare(want_grad)                 # (engine state NOT restored after the call; CXRBertForReportFinetune.forward restores it)
         params = list(self.bert._plist) + self._hplist
         if target is None:
             return _VQAFn.apply(self, "logits", cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, None, None, *params)
@@ -356,35 +229,12 @@ class CXRBertForVQA(nn.Module):
         if attn_mask.dim() not in (2, 3):
             raise NotImplementedError
         feats, pos = self.bert._regions(input_img)
-        eng = self.bert.engine
-        prev = (eng.training, eng.keep_acts)
-        try:
+        with self._engine_state("training", "keep_acts") as eng:
             self._prepare(False)
             logits = self._encode_and_classify(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, infer=True)
             ans = torch.empty(int(input_txt.shape[0]), dtype=torch.int64, device=eng.device)
             ops.bce_fwd_bwd(logits, self.n_answers, ld=self.Ap, arg_infer=ans)
-        finally:                # sticky engine state: a later direct Engine user must find what it left
-            eng.training, eng.keep_acts = prev
         return ans
-
-    # ------------------------------------------------------------------ optimizer hook (medvill_amd.optim.AdamW)
-    def _adamw_head(self, step, lr, betas, eps, weight_decay, correct_bias):
-        grads = [p.grad for p in self._hplist]
-        if all(g is None for g in grads):
-            return
-        if any(g is None for g in grads):
-            raise RuntimeError("some classifier Parameters have a gradient and some have none: the flat update cannot skip individual tensors")
-        if self.head_g is None:
-            self.head_g = torch.zeros_like(self.head_p)
-        for name, g in zip(self._head_keys, grads):
-            gv = self._view(self.head_g, name)
-            if g.data_ptr() != gv.data_ptr():
-                gv.copy_(g)
-        if self.head_m is None:
-            self.head_m, self.head_v = torch.zeros_like(self.head_p), torch.zeros_like(self.head_p)
-        ops.adamw_step(self.head_p, self.head_g, self.head_m, self.head_v, self.head_sh, self._n_head, lr, betas[0], betas[1], eps,
-                       weight_decay, step, correct_bias, 1.0, shadow_f16=self.head_shf)
-        self._head_versions = sum(p._version for p in self._hplist)      # the kernel has written the 16-bit copies too
 
     # ------------------------------------------------------------------ state dict (the reference's VQA layout)
     def state_dict(self, *a, **k):
@@ -392,9 +242,7 @@ class CXRBertForVQA(nn.Module):
         -- plus ans_classifier.{0,2}.{weight,bias}."""
         sd = self.bert.state_dict()
         out = to_finetune_keys(OrderedDict((k_, v) for k_, v in sd.items() if not k_.startswith(("mlm.", "itm."))))
-        for name, p in zip(HEAD_KEYS, self._hplist):
-            out[name] = p.detach().clone()
-        return out
+        return self._head_state(out)
 
     def load_state_dict(self, sd, strict=True):
         """A VQA-layout dict (finetune keys + ans_classifier.*) or a CXRBERT pretraining state dict (enc.* / mlm.* / itm.*; the
@@ -402,48 +250,17 @@ class CXRBertForVQA(nn.Module):
         head = {k_: v for k_, v in sd.items() if k_.startswith("ans_classifier.")}
         rest = OrderedDict((k_, v) for k_, v in sd.items() if not k_.startswith("ans_classifier."))
         pretraining = any(k_.startswith("enc.") for k_ in rest)
-        r = self.bert.load_state_dict(rest if pretraining else from_finetune_keys(rest), strict=False)
-        missing = [k_ for k_ in r.missing_keys if not k_.startswith(("mlm.", "itm."))]
-        unexpected = list(r.unexpected_keys) + [k_ for k_ in head if k_ not in HEAD_KEYS]
-        with torch.no_grad():
-            if head:
-                for name in HEAD_KEYS:
-                    if name in head:
-                        self._view(self.head_p, name).copy_(head[name].to(self.head_p.device, torch.float32))
-                    else:
-                        missing.append(name)
-            else:
-                self.reset_head()
-        self._head_versions = None
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"load_state_dict: missing {missing[:5]} unexpected {unexpected[:5]}")
-        return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
+        return self._load_state(head, rest if pretraining else from_finetune_keys(rest), strict)
 
     def save_pretrained(self, save_directory):
         """config.json + pytorch_model.bin in the reference's VQA layout."""
-        os.makedirs(save_directory, exist_ok=True)
-        c = self.bert.cfg
-        cj = dict(architectures=["CXRBertForVQA"], model_type="bert", vocab_size=c.vocab_size, hidden_size=c.hidden,
-                  num_hidden_layers=c.layers, num_attention_heads=c.heads, intermediate_size=c.intermediate,
-                  max_position_embeddings=c.max_pos, type_vocab_size=c.type_vocab, layer_norm_eps=c.ln_eps, hidden_act="gelu",
-                  hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, n_answers=self.n_answers)
-        with open(os.path.join(save_directory, "config.json"), "w") as f:
-            json.dump(cj, f, indent=2)
-        torch.save({k_: v.cpu() for k_, v in self.state_dict().items()}, os.path.join(save_directory, "pytorch_model.bin"))
+        write_pretrained(save_directory, hf_config(self.bert.cfg, "CXRBertForVQA", n_answers=self.n_answers), self.state_dict())
 
     @classmethod
     def from_pretrained(cls, path_or_state_dict, config=None, args=None, n_answers=None, **kw):
         """A checkpoint directory (config.json + pytorch_model.bin: CXRBERT.save_pretrained or save_pretrained above) or a state dict
         (then `config` is required) -> model.  A pretraining checkpoint initialises the classifier from torch.initial_seed()."""
-        if isinstance(path_or_state_dict, (str, os.PathLike)):
-            if config is None:
-                with open(os.path.join(path_or_state_dict, "config.json")) as f:
-                    config = json.load(f)
-            sd = torch.load(os.path.join(path_or_state_dict, "pytorch_model.bin"), map_location="cpu")
-        else:
-            sd = path_or_state_dict
-            if config is None:
-                raise ValueError("from_pretrained(state_dict): pass config= as well")
+        config, sd = read_pretrained(path_or_state_dict, config)
         if n_answers is None:
             w = sd.get(HEAD_KEYS[2])
             n_answers = int(w.shape[0]) if w is not None else int(config.get("n_answers", N_ANSWERS) if isinstance(config, dict) else N_ANSWERS)

@@ -248,7 +248,7 @@ def test_classification_class_is_exported_and_shaped():
     for n_, e in zip(m.bert._param_names, opt._entries()):
         assert e[3] == (not n_.startswith(("mlm.", "itm."))), n_
     assert [e[1] for e in opt._head_entries()] == [14 * 64, 14] and [e[2] for e in opt._head_entries()] == [True, False]
-    assert mv.optim.AdamW(m.parameters(), lr=1e-4)._vqa is m
+    assert mv.optim.AdamW(m.parameters(), lr=1e-4)._task is m
 
 
 def test_classification_checkpoint_layout_and_round_trips(tmp_path):

@@ -300,3 +300,29 @@ def test_short_finetune_with_bertadam_reaches_micro_f1_one():
     for k, p in m.bert.named_parameters():       # unreached heads: bit-unchanged under BertAdam
         if k.startswith(("mlm.", "itm.")):
             assert torch.equal(p.detach().cpu(), P[k].float()), k
+
+
+def test_overflowed_backward_is_redone_with_a_smaller_scale():
+    """f16 gradient operands under a loss scale far past f16's range: the backward overflows (the head's gradients included), redoes
+    itself with S / 16 until everything is finite and hands over the gradients of a twin run at the default scale."""
+    P = O.make_params(CFG, seed=3)
+    b = _batch("s2s")
+    grads = []
+    for scale in (2.0 ** 40, None):
+        m = _model(torch.bfloat16, P)
+        eng = m.bert.engine
+        assert eng.scaler is not None
+        loss = m(*_inputs(b), labels=b["labels"].to(DEV))
+        if scale is not None:
+            eng.reset_scaler(scale)
+        loss.backward()
+        if scale is not None:
+            assert float(eng.scaler[0]) < scale                      # the redo did happen
+        grads.append({k: g.detach().float().cpu() for k, g in _grads(m).items()})
+    got, twin = grads
+    assert all(bool(torch.isfinite(g).all()) for g in got.values())
+    off = ("itm.", "mlm.")                                            # as the oracle test: no gradient reaches them
+    for k, g in got.items():
+        if k.startswith(off):
+            assert float(g.abs().max()) == 0.0, k
+    _compare_grads(got, {k: g for k, g in twin.items() if not k.startswith(off)}, 3e-2)

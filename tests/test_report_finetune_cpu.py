@@ -220,15 +220,21 @@ def test_save_load_round_trips_and_generation_reads_the_directory(tmp_path):
             assert all(torch.equal(got[k], v) for k, v in want.items()), (cls.__name__, d)
 
 
-def test_forward_needs_the_three_lists_and_refuses_data_parallel_use():
+def test_forward_needs_the_three_lists_and_refuses_data_parallel_use(monkeypatch):
     m = mv.CXRBertForReportFinetune(TINY, dtype=torch.float32, device="cpu")
     z = torch.zeros(2, 5, dtype=torch.int64)
+    args = (z[:, :1], z, torch.ones(2, 11, 11, dtype=torch.int64), z, (torch.zeros(2, 4, 2048), z[:, :4]), z[:, :1])
     with pytest.raises(ValueError, match="masked_lm_labels"):
-        m(z[:, :1], z, torch.ones(2, 11, 11, dtype=torch.int64), z, (torch.zeros(2, 4, 2048), z[:, :4]), z[:, :1], masked_pos=z)
+        m(*args, masked_pos=z)
     with pytest.raises(ValueError):
         mv.CXRBertForReportFinetune(TINY, device="cpu", label_smoothing=1.5)
-    src = open(os.path.join(ROOT, "multi-modality-self-supervision_amd", "report_finetune.py")).read()
-    assert "_check_single_rank()" in src and "get_world_size() > 1" in src
+    import torch.distributed as dist
+    monkeypatch.setattr(dist, "is_available", lambda: True)
+    monkeypatch.setattr(dist, "is_initialized", lambda: True)
+    monkeypatch.setattr(dist, "get_world_size", lambda *a, **k: 2)
+    lists = dict(masked_lm_labels=torch.ones(2, 2, dtype=torch.int64), masked_pos=torch.full((2, 2), 7), masked_weights=torch.ones(2, 2))
+    with pytest.raises(RuntimeError, match="data-parallel"):
+        m(*args, **lists)
 
 
 # ------------------------------------------------------------------------------------------------ BertAdam's table

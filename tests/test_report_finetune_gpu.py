@@ -362,3 +362,29 @@ def test_finetune_save_and_decode_round_trip(tmp_path):
     ids_a, _ = m.bert.generate(*args, max_len=8)
     ids_b, _ = gen.generate(*args, max_len=8)
     assert torch.equal(ids_a, ids_b)
+
+
+def test_overflowed_backward_is_redone_with_a_smaller_scale():
+    """f16 gradient operands under a loss scale far past f16's range: the backward overflows, redoes itself with S / 16 until everything
+    is finite and hands over the gradients of a twin run at the default scale."""
+    P = O.make_params(CFG, seed=3)
+    b = _batch("s2s")
+    grads = []
+    for scale in (2.0 ** 40, None):
+        m = _model(torch.float16, P, 0.1)
+        eng = m.bert.engine
+        assert eng.scaler is not None
+        loss, _ = m(*_inputs(b), **_lists(b), drop_worst_ratio=0.0)
+        if scale is not None:
+            eng.reset_scaler(scale)
+        loss.backward()
+        if scale is not None:
+            assert float(eng.scaler[0]) < scale                      # the redo did happen
+        grads.append({k: (None if p.grad is None else p.grad.detach().float().cpu()) for k, p in m.bert.named_parameters()})
+    got, twin = grads
+    for k, g in got.items():
+        if k.startswith(UNREACHED):                                   # as the oracle test
+            assert g is None or float(g.abs().max()) == 0.0, k
+        else:
+            assert bool(torch.isfinite(g).all()), k
+    _compare_grads(got, {k: g for k, g in twin.items() if not k.startswith(UNREACHED)}, RTOL[torch.float16])

@@ -317,3 +317,28 @@ def test_checkpoint_round_trip(tmp_path):
     with torch.no_grad():
         a, b = m(*args), m2(*args)
     assert torch.equal(a, b) and not torch.equal(m.bert.engine.p["itm.linear.weight"].cpu(), P["itm.linear.weight"].float())
+
+
+def test_overflowed_backward_is_redone_with_a_smaller_scale():
+    """f16 gradient operands under a loss scale far past f16's range: the backward overflows, redoes itself with S / 16 until everything
+    is finite and hands over the gradients of a twin run at the default scale."""
+    P = O.make_params(CFG, seed=3)
+    b = _batch()
+    grads = []
+    for scale in (2.0 ** 40, None):
+        m = _model(torch.bfloat16, P)
+        eng = m.bert.engine
+        assert eng.scaler is not None
+        loss = m(*_inputs(b), labels=b["labels"].to(DEV))
+        if scale is not None:
+            eng.reset_scaler(scale)
+        loss.backward()
+        if scale is not None:
+            assert float(eng.scaler[0]) < scale                      # the redo did happen
+        grads.append({k: p.grad.detach().float().cpu() for k, p in m.bert.named_parameters()})
+    got, twin = grads
+    assert all(bool(torch.isfinite(g).all()) for g in got.values())
+    for k, g in got.items():                                          # as the oracle test: the MLM head's own tensors get none
+        if k.startswith("mlm."):
+            assert float(g.abs().max()) == 0.0, k
+    _compare_grads(got, {k: g for k, g in twin.items() if not k.startswith("mlm.")}, 3e-2)

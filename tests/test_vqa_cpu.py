@@ -117,7 +117,7 @@ def test_new_abi_entries_are_declared_exported_and_prototyped():
 def test_fused_adamw_takes_the_vqa_model_and_still_refuses_foreign_parameters():
     m = mv.CXRBertForVQA(TINY, device="cpu")
     opt = mv.optim.AdamW(m.parameters(), lr=1e-4)
-    assert opt._vqa is m and len(opt.param_groups) == 1
+    assert opt._task is m and len(opt.param_groups) == 1
     with pytest.raises(ValueError):
         mv.optim.AdamW(list(m.parameters()) + [nn.Parameter(torch.zeros(3))])
     with pytest.raises(ValueError):                          # part of the classifier only
@@ -128,7 +128,7 @@ def test_fused_adamw_takes_the_vqa_model_and_still_refuses_foreign_parameters():
     with pytest.raises(ValueError):
         mv.optim.AdamW(list(m.ans_classifier.parameters()))
     plain = mv.optim.AdamW(m.bert.parameters())              # the encoder alone, as before
-    assert plain._vqa is None
+    assert plain._task is None
 
 
 def test_training_under_several_ranks_is_refused(monkeypatch):

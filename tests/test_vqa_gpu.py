@@ -344,7 +344,7 @@ def test_fused_adamw_over_the_vqa_model_equals_a_torch_optimizer():
     lr = 1e-4
     opts = [mv.optim.AdamW(ms[0].parameters(), lr=lr), _TorchHFAdamW(ms[1].parameters(), lr=lr),
             torch.optim.AdamW(ms[2].parameters(), lr=lr, weight_decay=0.0, eps=1e-6)]
-    assert opts[0]._vqa is ms[0]
+    assert opts[0]._task is ms[0]
     start = ms[2].ans_classifier[2].weight.detach().clone()
     for _ in range(3):
         for m, opt in zip(ms, opts):
@@ -399,3 +399,29 @@ def test_no_grad_forward_keeps_no_activations():
     eng = m.bert.engine
     assert eng.S["keep"] is False and loss.grad_fn is None and logits.grad_fn is None
     assert "qkv0" not in eng._ws and "qkv_nk" in eng._ws            # one shared scratch set, no per-layer activations
+
+
+def test_overflowed_backward_is_redone_with_a_smaller_scale():
+    """f16 gradient operands under a loss scale far past f16's range: the backward overflows (the classifier's gradients included),
+    redoes itself with S / 16 until everything is finite and hands over the gradients of a twin run at the default scale."""
+    P = O.make_params(CFG, seed=3)
+    b = _batch("s2s")
+    grads = []
+    for scale in (2.0 ** 40, None):
+        m = _model(torch.bfloat16, P)
+        eng = m.bert.engine
+        assert eng.scaler is not None
+        _, loss = m(*_inputs(b), ans_labels=b["target"].to(DEV), ans_type=b["ans_type"].to(DEV))
+        if scale is not None:
+            eng.reset_scaler(scale)
+        loss.backward()
+        if scale is not None:
+            assert float(eng.scaler[0]) < scale                      # the redo did happen
+        grads.append({k: g.detach().float().cpu() for k, g in _grads(m).items()})
+    got, twin = grads
+    assert all(bool(torch.isfinite(g).all()) for g in got.values())
+    off = ("enc.pooler.", "itm.", "mlm.")                             # as the oracle test: no gradient reaches them
+    for k, g in got.items():
+        if k.startswith(off):
+            assert float(g.abs().max()) == 0.0, k
+    _compare_grads(got, {k: g for k, g in twin.items() if not k.startswith(off)}, 3e-2)
