@@ -164,7 +164,7 @@ class CXRBertForClassification(FlatHead):
         eng._dW(dl, eng.S["pooled"], self._view(self.head_g, CLF_KEYS[0]), C, H, B, lda=Cp, ldb=H)
         dpool = eng._buf("dpool", (B, H), adt)
         ops.gemm(dl, self._view(self._shadow_of(eng.dt), CLF_KEYS[0], padded=True), dpool, tb=True, M=B, N=H, K=Cp, lda=Cp, ldb=H)
-        eng.S["dhidden"] = eng._buf("dhidden_tail", (B, H), adt)       # the compact final state's gradient: the pooler path fills it
+        eng.dhidden_buffer()                                           # the compact final state's gradient: the pooler path fills it
         eng._pooler_backward(dpool)                                    # tanh backward, pooler gradients, dh[CLS]
         eng.encoder_backward()
 

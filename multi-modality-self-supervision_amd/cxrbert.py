@@ -116,20 +116,10 @@ class _CXRBertFn(torch.autograd.Function):
             S, H = eng.S, eng.cfg.hidden
             ls = eng.loss_scale_dev          # f16 gradients: the incoming f32 gradients enter the chain multiplied by S
             sc = (lambda t: t) if ls is None else (lambda t: t.float() * ls)
-            dh = S["dhidden"] = eng._buf("dhidden", (S["M"], H), eng.adt)
+            dh = eng.dhidden_buffer()
             dh.copy_(sc(g0.reshape(S["M"], H))) if g0 is not None else dh.zero_()
             if g1 is not None:
-                # pooled = tanh(hidden[:,0].Wp^T + bp)
-                from . import hip_ops as ops
-                B, Lq = S["B"], S["L"]
-                dpre = eng._buf("dpoolpre", (B, H), eng.adt)
-                ops.dact(1, sc(g1).to(eng.adt).contiguous(), S["pooled"], dpre, B * H)
-                ops.colsum(dpre, H, B, H, eng.g["enc.pooler.dense.bias"], accumulate=True, unscale=eng.unscale_dev)
-                eng._dW(dpre, S["hidden"], eng.g["enc.pooler.dense.weight"], H, H, B, lda=H, ldb=Lq * H)
-                dh0 = eng._buf("dh0", (B, H), eng.adt)
-                ops.gemm(dpre, eng.w["enc.pooler.dense.weight"], dh0, tb=True, M=B, N=H, K=H)
-                rows0 = (torch.arange(B, device=eng.device, dtype=torch.int32) * Lq)
-                ops.scatter_rows(dh0, H, rows0, B, H, dh, H, accumulate=True)
+                eng._pooler_backward(sc(g1).to(eng.adt).contiguous())       # pooled = tanh(hidden[:,0].Wp^T + bp)
         eng.encoder_backward()
 
     @staticmethod
@@ -337,8 +327,6 @@ class _HeadFn(torch.autograd.Function):
             out = torch.empty((R, 2), dtype=torch.float32, device=eng.device)
             ops.gemm(xf, eng.wf["itm.linear.weight"], out, M=R, N=2, K=H, bias=eng.p["itm.linear.bias"], epi=EPI_BIAS)
             return out.view(*x.shape[:-1], 2)
-        if not hasattr(eng, "S"):
-            eng.S = {}
         logits = eng._mlm_forward(xf, xb, R, "hm_", pad=False)
         # The engine's scratch buffers are cached by name: a second model.mlm(...) before this call's backward would overwrite what this
         # call saved.  The reference's nn.Module heads are re-entrant (two calls in one graph, gradient accumulation over two forwards),
@@ -390,8 +378,7 @@ class _HeadFn(torch.autograd.Function):
             dl = torch.empty((R, Vp), dtype=adt, device=dev)
             ops.cast2d(scaled(g32.view(R, V)), V, dl, Vp, R, V)
             dxr = eng._mlm_backward(dl, "hm_")
-            if eng._side is not None:
-                torch.cuda.current_stream().wait_stream(eng._side)     # the decoder's / transform's parameter gradients (side stream)
+            eng.join_side()                   # the decoder's / transform's parameter gradients (side stream)
             eng._dE_ev = None
             # (dxr is a view of a named scratch buffer of the engine: hand autograd a tensor of its own -- on the fp32 path `unscaled` is the
             # identity, and the next head backward would overwrite what this one returned)

@@ -18,12 +18,13 @@ from __future__ import annotations
 
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from dataclasses import asdict, dataclass
 
 import torch
 
 from . import hip_ops as ops
+from .data import MaskDesc
 from ._lib import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_D, EPI_BIAS_RES, EPI_BIAS_TANH, EPI_MUL, EPI_NONE, EPI_RES, MV_BF16, MV_F16,
                    MV_F32)
 
@@ -151,6 +152,13 @@ def _shared_stream(device, kind):
     return st
 
 
+# The last layer's row order with each sample's consumed rows first: the four outputs of mv_tail_perm (include/medvill.h)
+TailPlan = namedtuple("TailPlan", "perm newpos qlim sel")
+# What the layers of one encoder_backward share: streams, data-parallel hook, the queue of deferred weight gradients (None: every layer
+# launches its own), the layers after which a part of it is launched, and the scratch every layer rewrites
+_Backward = namedtuple("_Backward", "main side hook group flush_after dctx delta da dxb")
+
+
 class Engine:
     """dtype = torch.float32: the exact path (VALU kernels).  dtype = torch.bfloat16: the 16-bit MFMA path -- fp32 master
     weights, accumulation, LayerNorm / softmax statistics, losses and optimizer; every MFMA operand is 16 bits wide.
@@ -202,7 +210,9 @@ class Engine:
             self.scaler = torch.zeros(8, dtype=torch.float32, device=self.device)
             self.reset_scaler()
         self.shadow_dirty = True
+        self.S = {}                   # what the last forward saved for the heads and the backward (encoder_forward)
         self._ws = {}
+        self._rows_now = self._rows_cap = 0      # row count of the current forward and of its padded form (see _buf)
         self._gemm_ws = {}             # split-K workspaces, one per stream that runs split-K GEMMs (never shared across streams)
         self._side = None             # side HIP stream for the weight-gradient GEMMs of the backward
         self.training = False         # dropout is active only when True (CXRBERT.train() / TrainStep(train=True))
@@ -219,7 +229,6 @@ class Engine:
         # optimizer step on the side stream.
         self.dz_nt = os.environ.get("MV_DZ_NT", "1") != "0"
         self._w2t, self._w2t_ev, self._w2t_stale = None, None, True
-        self.head_on_side = True  # the tied decoder's weight gradient on the side stream (see _mlm_backward)
         self.fused_colsum = os.environ.get("MV_FUSED_COLSUM", "1") != "0"   # bias gradients from partial sums of the producing kernels
         # the weight gradients of all full-row layers in ONE persistent launch over full contractions instead of four split-K launches
         # (+ four reductions) per layer (include/medvill.h, mv_gemm_grouped_tn).  Undistributed steps only: under a
@@ -230,18 +239,9 @@ class Engine:
         # chain's LayerNorm / attention kernels of the next layers still run beside it (1 / 2 / 3 / 4 / 6 launches measured)
         self.grouped_dw_parts = max(0, int(os.environ.get("MV_GROUPED_DW_PARTS", "0")))
         self._dw_group = {}
-        self.head_params_on_side = True   # MLM head: decoder-bias column sums and the transform's parameter gradients on the side stream
-        self.late_opt_wait = True     # the forward's preparation kernels run under the optimizer's first kernel (encoder_forward)
-        self.itm_on_side = True       # ITM head on the side stream under the MLM head's decoder GEMM (heads_train)
-        # fused step, 16-bit path: MLM logits in the forward encoding (see _mlm_forward).  Off: the in-process A/B showed no gain
-        # (24.60 vs 24.58 ms, profiles/r03_notes.txt), so the logits stay f32
-        self.logits_16 = os.environ.get("MV_LOGITS_16", "0") == "1"
         self.tail_queries = os.environ.get("MV_TAIL_QUERIES", "1") != "0"    # last layer's attention: consumed rows only as queries (see encoder_forward)
-        self._mask_stream = None      # third stream: the attention-dropout keep-bits of every layer are generated at the start of a forward
         self._dE_ev = None
         self._opt_ev = None       # overlapped AdamW: parameter range -> event (see adamw_step)
-        self.head_splitk = True  # split-K for the decoder's input gradient (see _mlm_backward)
-        self.dw_splitk = 0      # weight gradients: 0 = the library fills the chip with split-K slabs; n > 1 caps the slab count
         self.drop_seed = (torch.initial_seed() ^ 0x5DEECE66D) & 0xFFFFFFFFFFFFFFFF
         self.drop_counter = 0
         self._bind()
@@ -321,35 +321,55 @@ class Engine:
         self.shadow_dirty = False
         self._w2t_stale = True
 
+    def _w2t_fill(self, l):
+        cfg = self.cfg
+        if self._w2t is None:
+            self._w2t = [torch.empty((cfg.intermediate, cfg.hidden), dtype=self.adt, device=self.device) for _ in range(cfg.layers)]
+        ops.transpose(self.w[f"enc.encoder.layer.{l}.output.dense.weight"], self._w2t[l], cfg.hidden, cfg.intermediate)
+
     def refresh_w2t(self, on_side=True):
         """Transposed bf16 copies of the FFN-down weights ([I, H] each) for the NT form of dz; enqueued on the side stream (idle
         outside the backward) so that the main stream only waits for an event at its first dz."""
         if not (self.dz_nt and self.is16):
             return
-        cfg = self.cfg
-        H, I = cfg.hidden, cfg.intermediate
-        if self._w2t is None:
-            self._w2t = [torch.empty((I, H), dtype=self.adt, device=self.device) for _ in range(cfg.layers)]
         main = torch.cuda.current_stream()
-        if self._side is None:
-            self._side = _shared_stream(self.device, "side")
-        side = self._side if (on_side and os.environ.get("MV_SINGLE_STREAM") != "1") else main
+        side = self.side_stream() if on_side else main
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            for l in range(cfg.layers):
-                ops.transpose(self.w[f"enc.encoder.layer.{l}.output.dense.weight"], self._w2t[l], H, I)
-            self._w2t_ev = torch.cuda.Event()
-            self._w2t_ev.record(side)
+            for l in range(self.cfg.layers):
+                self._w2t_fill(l)
+            self._w2t_ev = self._done(side)
         self._w2t_stale = False
 
+    # ------------------------------------------------------------------ streams
     def side_stream(self):
         """The engine's second HIP stream (weight gradients during the backward; idle otherwise), or the current stream under
-        MV_SINGLE_STREAM=1."""
+        MV_SINGLE_STREAM=1 (read at call time)."""
         if os.environ.get("MV_SINGLE_STREAM") == "1":
             return torch.cuda.current_stream()
         if self._side is None:
             self._side = _shared_stream(self.device, "side")
         return self._side
+
+    def mask_stream(self):
+        """The third stream (the keep-bits of a forward's attention dropout); MV_SINGLE_STREAM does not cover it."""
+        return _shared_stream(self.device, "mask")
+
+    @staticmethod
+    def _fork(main, side):
+        """`side` waits for everything `main` holds so far."""
+        side.wait_event(Engine._done(main))
+
+    @staticmethod
+    def _done(stream):
+        """A fresh event behind everything `stream` holds so far."""
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        return ev
+
+    def join_side(self):
+        """The current stream waits for what the side stream holds (the parameter gradients a head's backward left there)."""
+        torch.cuda.current_stream().wait_stream(self.side_stream())
 
     def zero_grad(self):
         self.ensure_grad()
@@ -397,7 +417,7 @@ class Engine:
             # packed rows: the row count changes from batch to batch -- allocate row-shaped scratch for the padded row count
             # once instead of growing it whenever a longer batch comes by
             cap = n
-            rows, rows_cap = getattr(self, "_rows_now", 0), getattr(self, "_rows_cap", 0)
+            rows, rows_cap = self._rows_now, self._rows_cap
             if rows_cap > rows > 0 and len(shape) > 0 and shape[0] == rows:
                 cap = n // rows * rows_cap
             elif t is not None and t.dtype == dtype:
@@ -407,8 +427,9 @@ class Engine:
         return t[:n].view(shape)
 
     def _pair(self, key, shape):
-        """(forward-encoding buffer, gradient-product-encoding buffer) of one stored activation: two buffers on the f16
-        forward path, one and the same otherwise.  The second is passed to the producing kernel as its extra output."""
+        """(forward-encoding buffer, gradient-product-encoding buffer) of one stored activation: two buffers when the encodings
+        differ (`dual`), one and the same otherwise.  In the forward they are named `x` / `x_b`: the producing kernel gets `x_b` as its
+        extra output when `dual`, and the saved-for-backward dictionaries keep the `_b` one."""
         f = self._buf(key, shape, self.fadt)
         return (f, self._buf(key + "_b", shape, self.adt)) if self.dual else (f, f)
 
@@ -435,7 +456,7 @@ class Engine:
         auto = auto and wb > 0
         ws = self._gemm_workspace(wb // 4) if auto else None
         # f16 gradients are loss-scaled: the weight gradient is un-scaled where it is written (alpha = 1 / S from the device)
-        ops.gemm(dy, x, gW, ta=True, tb=True, M=No, N=Ko, K=Mtok, lda=lda, ldb=ldb, ldc=ldc, splitk=self.dw_splitk if auto else 1, ws=ws,
+        ops.gemm(dy, x, gW, ta=True, tb=True, M=No, N=Ko, K=Mtok, lda=lda, ldb=ldb, ldc=ldc, splitk=0 if auto else 1, ws=ws,
                  alpha=self.unscale_dev)
 
     # ------------------------------------------------------------------ encoder forward
@@ -451,16 +472,10 @@ class Engine:
         projection, LayerNorm, FFN, LayerNorm: per-row work) runs on those R + B rows only, and so does its backward.
         Exact: the other rows' outputs are unused and their gradients are zero.  The final hidden state is then the compact
         [R + B, H] matrix (labelled rows first, in the order given, then the B first rows)."""
-        cfg, dt, adt, dev = self.cfg, self.dt, self.adt, self.device
-        fadt, dual = self.fadt, self.dual
-        wf = self.wf
-        H, A, I, D = cfg.hidden, cfg.heads, cfg.intermediate, cfg.img_hidden
-        dh = H // A
+        cfg = self.cfg
         B, T = input_txt.shape
         N = img_feats.shape[1]
         Lq = N + T + 2
-        M = B * Lq
-        from .data import MaskDesc
         if isinstance(attn_mask, MaskDesc):
             if attn_mask.desc.shape[0] != B or attn_mask.L != Lq:
                 raise ValueError(f"mask descriptors (B={attn_mask.desc.shape[0]}, L={attn_mask.L}) do not match B={B}, L={Lq}")
@@ -468,50 +483,61 @@ class Engine:
             raise ValueError(f"attn_mask shape {tuple(attn_mask.shape)} does not match L = N+T+2 = {Lq}")
         if self.shadow_dirty:
             self.sync_shadow()
-        if not self.late_opt_wait:
-            self._wait_opt("embeddings_rest")
-            self._wait_opt("embeddings")
-        f32 = torch.float32
-        S = self.S = dict(B=B, T=T, N=N, L=Lq, M=M, cu=None, rowmap=None, inv=None, sel=None, n_lab=0, tq=None)
+        S = self.S = dict(B=B, T=T, N=N, L=Lq, M=B * Lq, cu=None, rowmap=None, inv=None, sel=None, n_lab=0, tq=None, tail_sel=None, layers=[],
+                          p_drop=float(cfg.dropout) if self.training else 0.0, keep=bool(self.keep_acts))
+        self._row_plan(attn_mask, pack, tail_rows)
+        self.drop_counter += 1
+        S["drop_keys"] = self._drop_keys(cfg.layers)
+        feats_f = self._stage_inputs(cls_tok, input_txt, attn_mask, segment, img_feats, img_pos, sep_tok)
+        keep_bits = self._keep_bits() if S["p_drop"] > 0 else None
+        x, x_b = self._embed_forward(feats_f)
+        for l in range(cfg.layers):
+            x, x_b = self._layer_forward(l, x, x_b, keep_bits)
+        S["hidden_f"], S["hidden"] = x, x_b
+        pooled = self._pooler_forward(x, x_b)
+        return (x.view(B, Lq, cfg.hidden) if (S["cu"] is None and S["sel"] is None) else x), pooled
+
+    def _row_plan(self, attn_mask, pack, tail_rows):
+        """The packed-row plan (cu, rowmap, inv, M), the consumed rows (sel, n_lab) and the last layer's order (tq; tail_sel = sel in it)."""
+        S, dev = self.S, self.device
+        B, Lq = S["B"], S["L"]
         if pack:
             if not isinstance(attn_mask, MaskDesc) or not self.is16:
                 raise ValueError("pack=True needs mask descriptors (data.MaskDesc) and the bf16 path")
             hd = attn_mask.host_desc()
             if not bool(((hd[:, 0] == 0) | (hd[:, 0] == 1) | (hd[:, 0] == 4)).all()):
                 raise ValueError("pack=True: padding is visible to valid queries in the BAR / non-cross families")
-            M = int(hd[:, 2].clamp(0, Lq).sum())
+            S["M"] = int(hd[:, 2].clamp(0, Lq).sum())
             S["cu"], S["rowmap"], S["inv"] = ops.pack_plan(attn_mask.desc.to(dev), B, Lq)
-            S["M"] = M
+        M, cu = S["M"], S["cu"]
         self._rows_now, self._rows_cap = M, B * Lq
-        cu, rowmap = S["cu"], S["rowmap"]
-        if tail_rows is not None and cfg.layers >= 1:
-            lab = tail_rows.to(dev)
-            if S["inv"] is not None and lab.numel() > 0:     # logical flat positions -> packed rows
-                lab = S["inv"].index_select(0, lab.to(torch.int64))
-            first = cu[:B] if cu is not None else torch.arange(B, device=dev, dtype=torch.int32) * Lq
-            S["sel"] = torch.cat([lab.to(torch.int32), first.to(torch.int32)]).contiguous()
-            S["n_lab"] = int(tail_rows.numel())
-            # The consumed rows are also the only QUERIES the last layer's attention needs (its keys / values are all rows).  In the full /
-            # 1-D families a packed sample's mask is "every row sees every row" whatever the order of the rows, so the last layer runs on
-            # rows reordered with the consumed ones first and its attention kernels stop after them (mv_tail_perm, qlim): exact, and
-            # about 70 % of that layer's attention forward and backward is not computed.
-            S["tq"] = None
-            if pack and self.tail_queries and cfg.layers >= 1 and ops.get_impl() == 0 and Lq <= 2048 and \
-                    bool(((hd[:, 0] == 0) | (hd[:, 0] == 4)).all()):
-                S["tq"] = ops.tail_perm(cu, B, Lq, S["sel"], M)          # (perm, newpos, qlim, sel_new)
-        pd = S["p_drop"] = float(cfg.dropout) if self.training else 0.0
-        self.drop_counter += 1
-        dk = S["drop_keys"] = self._drop_keys(cfg.layers)
-        i64 = torch.int64
-        S["cls_tok"] = cls_tok.to(dev, i64).contiguous().view(-1)
-        S["sep_tok"] = sep_tok.to(dev, i64).contiguous().view(-1)
-        S["txt"] = input_txt.to(dev, i64).contiguous()
-        S["segment"] = segment.to(dev, i64).contiguous()
-        S["img_pos"] = img_pos.to(dev, i64).contiguous()
+        if tail_rows is None or self.cfg.layers < 1:
+            return
+        lab = tail_rows.to(dev)
+        if S["inv"] is not None and lab.numel() > 0:     # logical flat positions -> packed rows
+            lab = S["inv"].index_select(0, lab.to(torch.int64))
+        first = cu[:B] if cu is not None else torch.arange(B, device=dev, dtype=torch.int32) * Lq
+        S["sel"] = S["tail_sel"] = torch.cat([lab.to(torch.int32), first.to(torch.int32)]).contiguous()
+        S["n_lab"] = int(tail_rows.numel())
+        # The consumed rows are also the only QUERIES the last layer's attention needs (its keys / values are all rows).  In the full /
+        # 1-D families a packed sample's mask is "every row sees every row" whatever the order of the rows, so the last layer runs on
+        # rows reordered with the consumed ones first and its attention kernels stop after them (mv_tail_perm, qlim): exact, and
+        # about 70 % of that layer's attention forward and backward is not computed.
+        if pack and self.tail_queries and ops.get_impl() == 0 and Lq <= 2048 and bool(((hd[:, 0] == 0) | (hd[:, 0] == 4)).all()):
+            S["tq"] = TailPlan(*ops.tail_perm(cu, B, Lq, S["sel"], M))
+            S["tail_sel"] = S["tq"].sel
+
+    def _stage_inputs(self, cls_tok, input_txt, attn_mask, segment, img_feats, img_pos, sep_tok):
+        """Index tensors, region features (returned in the forward encoding) and the packed attention-mask words."""
+        S, dev = self.S, self.device
+        B, N, Lq = S["B"], S["N"], S["L"]
+        for key, t in (("cls_tok", cls_tok), ("sep_tok", sep_tok), ("txt", input_txt), ("segment", segment), ("img_pos", img_pos)):
+            S[key] = t.to(dev, torch.int64).contiguous()
+        S["cls_tok"], S["sep_tok"] = S["cls_tok"].view(-1), S["sep_tok"].view(-1)
         # region features -> operand encodings (the gradient-product copy is kept: the image projection's weight
         # gradient needs it)
-        feats_in = img_feats.to(dev).contiguous().view(B * N, D)
-        if feats_in.dtype not in (f32, torch.bfloat16, torch.float16):
+        feats_in = img_feats.to(dev).contiguous().view(B * N, self.cfg.img_hidden)
+        if feats_in.dtype not in (torch.float32, torch.bfloat16, torch.float16):
             feats_in = feats_in.float()
 
         def as_dtype(t, want, key):
@@ -520,49 +546,46 @@ class Engine:
             o = self._buf(key, tuple(t.shape), want)
             ops.cast(t, o, t.numel())
             return o
-        feats = S["feats"] = as_dtype(feats_in, adt, "feats")
-        feats_f = as_dtype(feats_in, fadt, "feats_f") if dual else feats
-        # packed mask
+        feats = S["feats"] = as_dtype(feats_in, self.adt, "feats")
+        feats_f = as_dtype(feats_in, self.fadt, "feats_f") if self.dual else feats
         W32, Tt = (Lq + 31) // 32, (Lq + 63) // 64
-        bits = self._buf("bits", (B, Lq, W32), torch.int32)
-        tinfo = self._buf("tinfo", (B, Tt, Tt), torch.uint8)
+        bits = S["bits"] = self._buf("bits", (B, Lq, W32), torch.int32)
+        tinfo = S["tinfo"] = self._buf("tinfo", (B, Tt, Tt), torch.uint8)
         if isinstance(attn_mask, MaskDesc):
             ops.mask_build(attn_mask.desc.to(dev), B, Lq, bits, tinfo)       # synthesised on the device, no [B,L,L] input
         else:
             ops.mask_pack(attn_mask.to(dev), bits, tinfo)
-        S["bits"], S["tinfo"] = bits, tinfo
         if bits.is_cuda:
-            S["bits_ev"] = torch.cuda.Event()
-            S["bits_ev"].record(torch.cuda.current_stream())
-        # image projection + embeddings
+            S["bits_ev"] = self._done(torch.cuda.current_stream())
+        return feats_f
+
+    def _keep_bits(self):
+        """Attention-probability dropout: the mask is a tensor of keep-bits (mv_attn_dropmask) that the forward and both backward
+        kernels select with.  It depends on the keys (and the packed lengths) only: all layers' bits are generated now, on their own
+        stream, under the embedding / first projection kernels.  Returns (bits, event) per layer."""
+        S, A = self.S, self.cfg.heads
+        ms = self.mask_stream()
+        ms.wait_stream(torch.cuda.current_stream())       # the previous step's backward has read the buffers; `cu` is ready
+        out = []
+        with torch.cuda.stream(ms):
+            for l in range(self.cfg.layers):
+                dbl = self._buf(f"dropbits{l}", (ops.dropbits_numel(S["B"], S["L"], A),), torch.int32)
+                ops.attn_dropmask(S["p_drop"], S["drop_keys"][(self.SITE_ATTN, l)], S["B"], S["L"], A, dbl, cu=S["cu"])
+                out.append((dbl, self._done(ms)))
+        return out
+
+    def _embed_forward(self, feats_f):
+        """Image projection + embeddings -> the first hidden state (x, x_b)."""
+        cfg, S, wf, f32 = self.cfg, self.S, self.wf, torch.float32
+        B, N, T, M, H = S["B"], S["N"], S["T"], S["M"], cfg.hidden
+        pd = S["p_drop"]
         e = "enc.txt_embeddings."
-        # Naming below: `x` / `x_b` etc. are the two encodings of one activation -- the forward operand (f16 on the default
-        # 16-bit path) and the copy the backward's gradient products read (bf16); they are the same buffer when the
-        # encodings coincide.  The saved-for-backward dictionaries keep the `_b` one.
-        xb2 = lambda f, b_: b_ if dual else None          # extra output of the producing kernel
-        db_ev = None
-        if pd > 0:
-            # attention-probability dropout: the mask is a tensor of keep-bits (mv_attn_dropmask) that the forward and both backward
-            # kernels select with.  It depends on the keys (and the packed lengths) only: all layers' bits are generated now, on
-            # their own stream, under the embedding / first projection kernels
-            if self._mask_stream is None:
-                self._mask_stream = _shared_stream(dev, "mask")
-            ms, main_ = self._mask_stream, torch.cuda.current_stream()
-            ms.wait_stream(main_)                     # the previous step's backward has read the buffers; `cu` is ready
-            db_ev = []
-            with torch.cuda.stream(ms):
-                for l in range(cfg.layers):
-                    dbl = self._buf(f"dropbits{l}", (ops.dropbits_numel(B, Lq, A),), torch.int32)
-                    ops.attn_dropmask(pd, dk[(self.SITE_ATTN, l)], B, Lq, A, dbl, cu=cu)
-                    ev = torch.cuda.Event()
-                    ev.record(ms)
-                    db_ev.append((dbl, ev))
         phase("embed")
-        imgproj = self._buf("imgproj", (B * N, H), fadt)
-        # first reader of the embeddings parameter range: everything above (row plan, mask words, keep-bits of every layer) did not need
+        imgproj = self._buf("imgproj", (B * N, H), self.fadt)
+        # first reader of the embeddings parameter range: everything before (row plan, mask words, keep-bits of every layer) did not need
         # the optimizer's first kernel (113 us over the word table) and ran under it
         self._wait_opt("embeddings_rest")
-        ops.gemm(feats_f, wf["enc.img_embeddings.img_embeddings.weight"], imgproj, M=B * N, N=H, K=D,
+        ops.gemm(feats_f, wf["enc.img_embeddings.img_embeddings.weight"], imgproj, M=B * N, N=H, K=cfg.img_hidden,
                  bias=self.p["enc.img_embeddings.img_embeddings.bias"], epi=EPI_BIAS)
         self._wait_opt("embeddings")                # the word table
         x, x_b = self._pair("x0", (M, H))
@@ -575,83 +598,93 @@ class Engine:
                       wf[e + "word_embeddings.weight"], wf[e + "position_embeddings.weight"],
                       wf[e + "token_type_embeddings.weight"], self.p[e + "LayerNorm.weight"], self.p[e + "LayerNorm.bias"],
                       x, pre0, mean0, rstd0, B, N, T, H, cfg.vocab_size, cfg.max_pos, cfg.ln_eps, p_drop=pd,
-                      drop_key=dk[(self.SITE_EMB, 0)], rowmap=rowmap, n_rows=M, x0_bf16=xb2(x, x_b), p_drop_img=pdi)
-        S["layers"] = []
-        # keep_acts False (a forward nothing will back-propagate through: torch.no_grad() / eval scoring): the per-layer activations are
-        # not kept -- every layer writes the same scratch set (12 x 0.95 GB -> 0.95 GB at B = 64, L = 512) and S["layers"] is not a
-        # valid input of encoder_backward
-        keep = S["keep"] = bool(self.keep_acts)
-        for l in range(cfg.layers):
-            lk = l if keep else "_nk"
-            phase(f"layer{l}.attention")
-            self._wait_opt(f"layer{l}")
-            p = f"enc.encoder.layer.{l}."
-            Wqkv, bqkv, _, _ = self.qkv_views(l, fwd=True)
-            a_ = {}
-            tq = S["tq"] if l == cfg.layers - 1 else None
-            if tq is not None:
-                # last layer on the reordered rows (consumed rows first within each sample); its output only exists on the consumed rows
-                xp, xp_b = self._pair("tail_xperm", (M, H))
-                ops.gather_rows(x, H, tq[0], M, H, xp, H)
-                if dual:
-                    ops.gather_rows(x_b, H, tq[0], M, H, xp_b, H)
-                x, x_b = xp, xp_b
-            a_["x"] = x_b
-            qkv, qkv_b = self._pair(f"qkv{lk}", (M, 3 * H))
-            a_["qkv"] = qkv_b
-            ops.gemm(x, Wqkv, qkv, M=M, N=3 * H, K=H, bias=bqkv, epi=EPI_BIAS, c3=xb2(qkv, qkv_b))
-            ctx, ctx_b = self._pair(f"ctx{lk}", (M, H))
-            a_["ctx"] = ctx_b
-            lse = a_["lse"] = self._buf(f"lse{lk}", (B, A, Lq), f32)
-            a_["dropbits"] = None
-            if db_ev is not None:
-                a_["dropbits"] = db_ev[l][0]
-                torch.cuda.current_stream().wait_event(db_ev[l][1])
-            ops.attn_fwd(qkv, bits, tinfo, ctx, lse, B, Lq, A, dh, p_drop=pd, cu=cu,
-                         total_rows=M, ctx_bf16=xb2(ctx, ctx_b), dropbits=a_["dropbits"], qlim=tq[2] if tq is not None else None)
-            Mr = M                  # rows the rest of this layer runs on
-            if l == cfg.layers - 1 and S["sel"] is not None:
-                # last layer: only the labelled rows and the first row of every sample are consumed downstream
-                sel = S["sel"] if tq is None else tq[3]
-                Mr = int(sel.numel())
-                ctx_s, ctx_sb = self._pair("tail_ctx", (Mr, H))
-                x_s = self._buf("tail_x", (Mr, H), fadt)
-                ops.gather_rows(ctx, H, sel, Mr, H, ctx_s, H)
-                ops.gather_rows(x, H, sel, Mr, H, x_s, H)
-                if dual:
-                    ops.gather_rows(ctx_b, H, sel, Mr, H, ctx_sb, H)
-                ctx, x = ctx_s, x_s
-                a_["ctx_tail"] = ctx_sb
-            a_["rows"] = Mr
-            M_all, M = M, Mr        # (restored after the layer; nothing follows the last layer)
-            pre_dt = self.fadt if (self.fdt == MV_F16 and self.ln_in_16) else f32
-            pre1 = a_["pre1"] = self._buf(f"pre1_{lk}" + ("h" if pre_dt != f32 else ""), (M, H), pre_dt)
-            ops.gemm(ctx, wf[p + "attention.output.dense.weight"], pre1, M=M, N=H, K=H,
-                     bias=self.p[p + "attention.output.dense.bias"], epi=EPI_BIAS_RES, r=x, p_drop=pd,
-                     drop_key=dk[(self.SITE_OUT1, l)])
-            a1, a1_b = self._pair(f"a{lk}", (M, H))
-            a_["a"] = a1_b
-            a_["mean1"], a_["rstd1"] = self._buf(f"mean1_{lk}", (M,), f32), self._buf(f"rstd1_{lk}", (M,), f32)
-            ops.layernorm_fwd(pre1, self.p[p + "attention.output.LayerNorm.weight"], self.p[p + "attention.output.LayerNorm.bias"],
-                              a1, a_["mean1"], a_["rstd1"], M, H, cfg.ln_eps, y_bf16=xb2(a1, a1_b))
-            phase(f"layer{l}.ffn")
-            act, act_b = self._pair(f"i{lk}", (M, I))
-            a_["i"] = act_b
-            # the second output is gelu'(z), not z: the derivative shares the forward's exp / reciprocal, and the backward
-            # GEMM then only multiplies by it (an elementwise operand: either encoding serves)
-            dg = a_["dgelu"] = self._buf(f"dgelu{lk}", (M, I), fadt)
-            ops.gemm(a1, wf[p + "intermediate.dense.weight"], act, M=M, N=I, K=H, bias=self.p[p + "intermediate.dense.bias"],
-                     epi=EPI_BIAS_GELU_D, c2=dg, c3=xb2(act, act_b))
-            pre2 = a_["pre2"] = self._buf(f"pre2_{lk}" + ("h" if pre_dt != f32 else ""), (M, H), pre_dt)
-            ops.gemm(act, wf[p + "output.dense.weight"], pre2, M=M, N=H, K=I, bias=self.p[p + "output.dense.bias"],
-                     epi=EPI_BIAS_RES, r=a1, p_drop=pd, drop_key=dk[(self.SITE_OUT2, l)])
-            x, x_b = self._pair(f"x{l + 1}" if keep else f"x_pp{l & 1}", (M, H))
-            a_["mean2"], a_["rstd2"] = self._buf(f"mean2_{lk}", (M,), f32), self._buf(f"rstd2_{lk}", (M,), f32)
-            ops.layernorm_fwd(pre2, self.p[p + "output.LayerNorm.weight"], self.p[p + "output.LayerNorm.bias"], x, a_["mean2"],
-                              a_["rstd2"], M, H, cfg.ln_eps, y_bf16=xb2(x, x_b))
-            M = M_all
-            S["layers"].append(a_)
-        S["hidden_f"], S["hidden"] = x, x_b
+                      drop_key=S["drop_keys"][(self.SITE_EMB, 0)], rowmap=S["rowmap"], n_rows=M, x0_bf16=x_b if self.dual else None,
+                      p_drop_img=pdi)
+        return x, x_b
+
+    def _layer_forward(self, l, x, x_b, keep_bits):
+        """Encoder layer l on the hidden state (x, x_b): appends what its backward needs to S["layers"], returns the next hidden state."""
+        cfg, S, wf, f32, dual = self.cfg, self.S, self.wf, torch.float32, self.dual
+        H, A, I = cfg.hidden, cfg.heads, cfg.intermediate
+        B, Lq, M, cu = S["B"], S["L"], S["M"], S["cu"]
+        pd, dk = S["p_drop"], S["drop_keys"]
+        last = l == cfg.layers - 1
+        # keep False (Engine.keep_acts: a forward nothing will back-propagate through, torch.no_grad() / eval scoring): the per-layer
+        # activations are not kept -- every layer writes the same scratch set (12 x 0.95 GB -> 0.95 GB at B = 64, L = 512) and S["layers"]
+        # is not a valid input of encoder_backward
+        lk = l if S["keep"] else "_nk"
+        phase(f"layer{l}.attention")
+        self._wait_opt(f"layer{l}")
+        p = f"enc.encoder.layer.{l}."
+        Wqkv, bqkv, _, _ = self.qkv_views(l, fwd=True)
+        a_ = {}
+        tq = S["tq"] if last else None
+        if tq is not None:
+            # last layer on the reordered rows (consumed rows first within each sample); its output only exists on the consumed rows
+            xp, xp_b = self._pair("tail_xperm", (M, H))
+            ops.gather_rows(x, H, tq.perm, M, H, xp, H)
+            if dual:
+                ops.gather_rows(x_b, H, tq.perm, M, H, xp_b, H)
+            x, x_b = xp, xp_b
+        a_["x"] = x_b
+        qkv, qkv_b = self._pair(f"qkv{lk}", (M, 3 * H))
+        a_["qkv"] = qkv_b
+        ops.gemm(x, Wqkv, qkv, M=M, N=3 * H, K=H, bias=bqkv, epi=EPI_BIAS, c3=qkv_b if dual else None)
+        ctx, ctx_b = self._pair(f"ctx{lk}", (M, H))
+        a_["ctx"] = ctx_b
+        lse = a_["lse"] = self._buf(f"lse{lk}", (B, A, Lq), f32)
+        a_["dropbits"] = None
+        if keep_bits is not None:
+            a_["dropbits"], ev = keep_bits[l]
+            torch.cuda.current_stream().wait_event(ev)
+        ops.attn_fwd(qkv, S["bits"], S["tinfo"], ctx, lse, B, Lq, A, H // A, p_drop=pd, cu=cu,
+                     total_rows=M, ctx_bf16=ctx_b if dual else None, dropbits=a_["dropbits"], qlim=tq.qlim if tq is not None else None)
+        if last and S["sel"] is not None:
+            # last layer: only the labelled rows and the first row of every sample are consumed downstream.  From here on M is the
+            # number of those rows
+            sel = S["tail_sel"]
+            M = int(sel.numel())
+            ctx_s, ctx_sb = self._pair("tail_ctx", (M, H))
+            x_s = self._buf("tail_x", (M, H), self.fadt)
+            ops.gather_rows(ctx, H, sel, M, H, ctx_s, H)
+            ops.gather_rows(x, H, sel, M, H, x_s, H)
+            if dual:
+                ops.gather_rows(ctx_b, H, sel, M, H, ctx_sb, H)
+            ctx, x = ctx_s, x_s
+            a_["ctx_tail"] = ctx_sb
+        a_["rows"] = M                  # rows the rest of this layer runs on
+        pre_dt = self.fadt if (self.fdt == MV_F16 and self.ln_in_16) else f32
+        pre1 = a_["pre1"] = self._buf(f"pre1_{lk}" + ("h" if pre_dt != f32 else ""), (M, H), pre_dt)
+        ops.gemm(ctx, wf[p + "attention.output.dense.weight"], pre1, M=M, N=H, K=H,
+                 bias=self.p[p + "attention.output.dense.bias"], epi=EPI_BIAS_RES, r=x, p_drop=pd,
+                 drop_key=dk[(self.SITE_OUT1, l)])
+        a1, a1_b = self._pair(f"a{lk}", (M, H))
+        a_["a"] = a1_b
+        a_["mean1"], a_["rstd1"] = self._buf(f"mean1_{lk}", (M,), f32), self._buf(f"rstd1_{lk}", (M,), f32)
+        ops.layernorm_fwd(pre1, self.p[p + "attention.output.LayerNorm.weight"], self.p[p + "attention.output.LayerNorm.bias"],
+                          a1, a_["mean1"], a_["rstd1"], M, H, cfg.ln_eps, y_bf16=a1_b if dual else None)
+        phase(f"layer{l}.ffn")
+        act, act_b = self._pair(f"i{lk}", (M, I))
+        a_["i"] = act_b
+        # the second output is gelu'(z), not z: the derivative shares the forward's exp / reciprocal, and the backward
+        # GEMM then only multiplies by it (an elementwise operand: either encoding serves)
+        dg = a_["dgelu"] = self._buf(f"dgelu{lk}", (M, I), self.fadt)
+        ops.gemm(a1, wf[p + "intermediate.dense.weight"], act, M=M, N=I, K=H, bias=self.p[p + "intermediate.dense.bias"],
+                 epi=EPI_BIAS_GELU_D, c2=dg, c3=act_b if dual else None)
+        pre2 = a_["pre2"] = self._buf(f"pre2_{lk}" + ("h" if pre_dt != f32 else ""), (M, H), pre_dt)
+        ops.gemm(act, wf[p + "output.dense.weight"], pre2, M=M, N=H, K=I, bias=self.p[p + "output.dense.bias"],
+                 epi=EPI_BIAS_RES, r=a1, p_drop=pd, drop_key=dk[(self.SITE_OUT2, l)])
+        x, x_b = self._pair(f"x{l + 1}" if S["keep"] else f"x_pp{l & 1}", (M, H))
+        a_["mean2"], a_["rstd2"] = self._buf(f"mean2_{lk}", (M,), f32), self._buf(f"rstd2_{lk}", (M,), f32)
+        ops.layernorm_fwd(pre2, self.p[p + "output.LayerNorm.weight"], self.p[p + "output.LayerNorm.bias"], x, a_["mean2"],
+                          a_["rstd2"], M, H, cfg.ln_eps, y_bf16=x_b if dual else None)
+        S["layers"].append(a_)
+        return x, x_b
+
+    def _pooler_forward(self, x, x_b):
+        """pooled = tanh(Wp . h[first row of every sample] + bp) from the final hidden state (x, x_b)."""
+        S, H = self.S, self.cfg.hidden
+        B, cu = S["B"], S["cu"]
         phase("heads")
         pooled, pooled_b = self._pair("pooled", (B, H))
         S["pooled_f"], S["pooled"] = pooled, pooled_b
@@ -659,17 +692,17 @@ class Engine:
             R_ = S["n_lab"]                               # compact final hidden state: the B first rows follow the labelled ones
             h0_f, S["h0"], S["h0_ld"] = x[R_:], x_b[R_:], H
         elif cu is None:
-            h0_f, S["h0"], S["h0_ld"] = x, x_b, Lq * H    # first row of every sample, addressed in place
+            h0_f, S["h0"], S["h0_ld"] = x, x_b, S["L"] * H    # first row of every sample, addressed in place
         else:
             h0_f, S["h0"] = self._pair("h0", (B, H))
             S["h0_ld"] = H
             ops.gather_rows(x, H, cu, B, H, h0_f, H)
-            if dual:
+            if self.dual:
                 ops.gather_rows(x_b, H, cu, B, H, S["h0"], H)
         self._wait_opt("heads")
-        ops.gemm(h0_f, wf["enc.pooler.dense.weight"], pooled, M=B, N=H, K=H, lda=S["h0_ld"],
-                 bias=self.p["enc.pooler.dense.bias"], epi=EPI_BIAS_TANH, c3=xb2(pooled, pooled_b))
-        return (x.view(B, Lq, H) if (cu is None and S["sel"] is None) else x), pooled
+        ops.gemm(h0_f, self.wf["enc.pooler.dense.weight"], pooled, M=B, N=H, K=H, lda=S["h0_ld"],
+                 bias=self.p["enc.pooler.dense.bias"], epi=EPI_BIAS_TANH, c3=pooled_b if self.dual else None)
+        return pooled
 
     # ------------------------------------------------------------------ heads (shared pieces)
     def _itm_forward(self):
@@ -678,11 +711,9 @@ class Engine:
         ops.gemm(S["pooled_f"], self.wf["itm.linear.weight"], itm, M=S["B"], N=2, K=H, bias=self.p["itm.linear.bias"], epi=EPI_BIAS)
         return itm
 
-    def _mlm_forward(self, xr, xr_b, R, tag, pad=True, logits16=False):
+    def _mlm_forward(self, xr, xr_b, R, tag, pad=True):
         """xr [R,H] (forward encoding; xr_b = its gradient-product copy) -> logits [R, Vp] f32 (Vp = V rounded up to 8
-        when `pad`; pad columns unspecified).  logits16 (fused training step, 16-bit path): the logits in the forward encoding -- they
-        only feed the fused cross-entropy, which computes in f32 from them (what autocast-style mixed precision does); halves the
-        decoder's output traffic and the loss kernel's input."""
+        when `pad`; pad columns unspecified)."""
         cfg, H, V = self.cfg, self.cfg.hidden, self.cfg.vocab_size
         f32 = torch.float32
         Vp = (V + 7) // 8 * 8 if pad else V
@@ -698,7 +729,7 @@ class Engine:
         ops.layernorm_fwd(tact, self.p["mlm.predictions.transform.LayerNorm.weight"],
                           self.p["mlm.predictions.transform.LayerNorm.bias"], t, hs["mean"], hs["rstd"], R, H, cfg.head_ln_eps,
                           y_bf16=t_b if self.dual else None)
-        logits = hs["logits"] = torch.empty((R, Vp), dtype=self.fadt if (logits16 and self.is16 and not self.dual) else f32, device=self.device)
+        logits = hs["logits"] = torch.empty((R, Vp), dtype=f32, device=self.device)
         ops.gemm(t, self.wf["enc.txt_embeddings.word_embeddings.weight"], logits, M=R, N=V, K=H, ldc=Vp,
                  bias=self.p["mlm.predictions.bias"], epi=EPI_BIAS)
         return logits
@@ -712,23 +743,16 @@ class Engine:
         # tied decoder: dE = dlogits^T . t  (the embedding scatter-add comes later, in embed_bwd).  360 tiles, no split-K, no
         # workspace: it runs on the side stream, which is idle until the encoder's backward starts; embed_bwd waits for it.
         # The decoder bias gradient (column sums over the 207 MB of dlogits) goes with it: nothing on the main chain needs it.
-        main = torch.cuda.current_stream()
-        if self._side is None:
-            self._side = _shared_stream(self.device, "side")
-        side = self._side if (self.head_on_side and os.environ.get("MV_SINGLE_STREAM") != "1") else main
+        main, side = torch.cuda.current_stream(), self.side_stream()
         side.wait_stream(main)
-        if not self.head_params_on_side:
-            ops.colsum(dlogits, Vp, R, V, g["mlm.predictions.bias"], accumulate=True, unscale=us)
         with torch.cuda.stream(side):
-            if self.head_params_on_side:
-                ops.colsum(dlogits, Vp, R, V, g["mlm.predictions.bias"], accumulate=True, unscale=us)
+            ops.colsum(dlogits, Vp, R, V, g["mlm.predictions.bias"], accumulate=True, unscale=us)
             self._dW(dlogits, hs["t"], g["enc.txt_embeddings.word_embeddings.weight"], V, H, R, lda=Vp, ldb=H)
-            self._dE_ev = torch.cuda.Event()
-            self._dE_ev.record(side)
-        if side is not main:
+            self._dE_ev = self._done(side)
+        if side != main:
             dlogits.record_stream(side)     # a per-step allocation of the caller: not to be reused before the side stream has read it
         dt_ = self._buf(tag + "dt", (R, H), self.adt)
-        wb = ops.gemm_workspace_bytes(self.adt, False, True, R, H, V) if (self.is16 and self.head_splitk and R * H <= 4 * 1024 * 1024) else 0
+        wb = ops.gemm_workspace_bytes(self.adt, False, True, R, H, V) if (self.is16 and R * H <= 4 * 1024 * 1024) else 0
         if wb > 0:
             # dt = dlogits . E contracts over the vocabulary (K = 30,522) into a [R, 768] result: 156 tiles of 128x128 for the
             # ~3,300 labelled rows -- a fifth of the chip's tile slots, 477 K-steps each.  Split-K (partial sums in f32, one
@@ -751,10 +775,9 @@ class Engine:
             tzc = hs["tz"]
         dtz = self._buf(tag + "dtz", (R, H), self.adt)
         ops.dact(0, dtact, tzc, dtz, R * H)
-        pside = side if self.head_params_on_side else main
-        if pside is not main:          # the transform's bias / weight gradients: parameter gradients, off the main chain like the encoder's
-            pside.wait_stream(main)
-        with torch.cuda.stream(pside):
+        if side != main:               # the transform's bias / weight gradients: parameter gradients, off the main chain like the encoder's
+            side.wait_stream(main)
+        with torch.cuda.stream(side):
             ops.colsum(dtz, H, R, H, g["mlm.predictions.transform.dense.bias"], accumulate=True, unscale=us)
             self._dW(dtz, hs["xr"], g["mlm.predictions.transform.dense.weight"], H, H, R, lda=H, ldb=H)
         dxr = self._buf(tag + "dxr", (R, H), self.adt)
@@ -795,6 +818,15 @@ class Engine:
             rows0 = S["cu"]                              # packed: sample b starts at row cu[b]
         ops.scatter_rows(dh0, H, rows0, B, H, S["dhidden"], H, accumulate=True)
 
+    def dhidden_buffer(self):
+        """The buffer for the gradient of the final hidden state, registered as S["dhidden"]: [n_lab + B, H] after a forward with
+        tail_rows (its compact final state), [M, H] otherwise.  Not cleared: a caller that does not write every row zeroes it."""
+        S = self.S
+        compact = S["sel"] is not None
+        rows = S["n_lab"] + S["B"] if compact else S["M"]
+        dh = S["dhidden"] = self._buf("dhidden_tail" if compact else "dhidden", (rows, self.cfg.hidden), self.adt)
+        return dh
+
     # ------------------------------------------------------------------ drop-in heads: full logits
     def heads_full(self):
         """(mlm [B,L,V] f32, itm [B,2] f32) over ALL positions -- the CXRBERT.forward contract."""
@@ -809,7 +841,7 @@ class Engine:
         Vp = (V + 7) // 8 * 8
         self.S.setdefault("hf_", {})["Vp"] = Vp
         self.ensure_grad()
-        dhid = S["dhidden"] = self._buf("dhidden", (M, H), self.adt)
+        dhid = self.dhidden_buffer()
         ls = self.loss_scale_dev                # f16 gradients: the incoming f32 gradients enter the chain multiplied by S
         if dmlm is not None:
             dl = torch.empty((M, Vp), dtype=self.adt, device=self.device)
@@ -842,27 +874,20 @@ class Engine:
         stats = torch.zeros(6, dtype=torch.float32, device=self.device)
         if compute_grad:
             self.ensure_grad()
-            if compact:
-                dhid = S["dhidden"] = self._buf("dhidden_tail", (R + B, H), self.adt)
-            else:
-                dhid = S["dhidden"] = self._buf("dhidden", (M, H), self.adt)
+            dhid = self.dhidden_buffer()
+            if not compact:
                 dhid.zero_()
         # The ITM head (pooler -> 2-way classifier, its loss and backward: a dozen latency-bound launches on [B, H] matrices, ~100 us in a
         # row) runs on the side stream, which is idle until the encoder's backward, under the MLM head's decoder GEMM on the main stream.
         # The two heads touch disjoint rows of dhidden, disjoint statistics and disjoint parameter gradients.
         main = torch.cuda.current_stream() if self.device.type == "cuda" else None
-        side = main
-        if main is not None and self.itm_on_side and os.environ.get("MV_SINGLE_STREAM") != "1":
-            if self._side is None:
-                self._side = _shared_stream(self.device, "side")
-            side = self._side
-        if side is not main:
+        side = self.side_stream() if main is not None else None
+        if side != main:
             side.wait_stream(main)
             stats.record_stream(side)
             with torch.cuda.stream(side):
                 self._itm_head(stats, is_aligned, B, itm_scale, itm_scale_dev, compute_grad)
-                itm_ev = torch.cuda.Event()       # main joins the ITM head alone, not what _mlm_backward queues behind it on this stream
-                itm_ev.record(side)
+                itm_ev = self._done(side)         # main joins the ITM head alone, not what _mlm_backward queues behind it on this stream
         if R > 0:
             if compact:
                 xr, xr_b = S["hidden_f"][:R], S["hidden"][:R]
@@ -871,7 +896,7 @@ class Engine:
                 ops.gather_rows(S["hidden_f"], H, label_rows, R, H, xr, H)
                 if self.dual:
                     ops.gather_rows(S["hidden"], H, label_rows, R, H, xr_b, H)
-            logits = self._mlm_forward(xr, xr_b, R, "ht_", logits16=self.logits_16)
+            logits = self._mlm_forward(xr, xr_b, R, "ht_")
             Vp = logits.shape[1]
             dl = torch.empty((R, Vp), dtype=self.adt, device=self.device) if compute_grad else None
             ops.ce_fwd_bwd(logits, Vp, label_ids, R, V, stats[0:3], dl, Vp, grad_scale_dev=mlm_scale_dev,
@@ -882,7 +907,7 @@ class Engine:
                     dhid[:R].copy_(dxr)
                 else:
                     ops.scatter_rows(dxr, H, label_rows, R, H, dhid, H, accumulate=False)
-        if side is main:
+        if side == main:
             self._itm_head(stats, is_aligned, B, itm_scale, itm_scale_dev, compute_grad)
         else:
             main.wait_event(itm_ev)     # (the tied decoder's dW, the decoder-bias sums and the transform's dW stay off the main chain: _dE_ev)
@@ -908,176 +933,45 @@ class Engine:
 
         bucket_hook(name, event) is called when the gradients of a contiguous parameter range are final on the side
         stream ('heads', 'layer<l>', 'embeddings') so a data-parallel driver can start its all-reduce."""
-        cfg, S = self.cfg, self.S
+        cfg, S, adt = self.cfg, self.S, self.adt
         if not S.get("keep", True):
             raise RuntimeError("encoder_backward after a forward that kept no activations (Engine.keep_acts = False / torch.no_grad())")
-        H, A, I, D = cfg.hidden, cfg.heads, cfg.intermediate, cfg.img_hidden
-        dh = H // A
-        B, Lq, M, N, T = S["B"], S["L"], S["M"], S["N"], S["T"]
-        adt, g, us = self.adt, self.g, self.unscale_dev
-        dy = S["dhidden"]
-        main = torch.cuda.current_stream()
-        if self._side is None:
-            self._side = _shared_stream(self.device, "side")
-        side = main if os.environ.get("MV_SINGLE_STREAM") == "1" else self._side     # measurement switch
+        H, I, M = cfg.hidden, cfg.intermediate, S["M"]
+        main, side = torch.cuda.current_stream(), self.side_stream()
         side.wait_stream(main)              # the heads' gradients and the zeroed flat gradient are ordered before us
-
-        def fork():
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
-
-        def side_done():
-            ev = torch.cuda.Event()
-            ev.record(side)
-            return ev
-
         if bucket_hook:
             # the MLM head's parameter gradients were written on the side stream (heads_train joins the ITM head only)
-            bucket_hook("heads", side_done() if side is not main else None)
-        use_w2t = self.dz_nt and self.is16
-        mfma_on = self.fused_colsum and self.is16 and ops.get_impl() == 0       # partial column sums exist in the MFMA kernels only
-        if use_w2t:
+            bucket_hook("heads", self._done(side) if side != main else None)
+        if self.dz_nt and self.is16:
             if self._w2t_stale or self._w2t is None:
                 self.refresh_w2t(on_side=False)
             main.wait_event(self._w2t_ev)
-        pd, dk = S["p_drop"], S["drop_keys"]
         # deferred weight gradients (see grouped_dw): (dy, x, gW, No, Ko, rows, lda, ldb, ldc) of the full-row layers
         group = [] if (self.grouped_dw and bucket_hook is None and self.is16 and ops.get_impl() == 0 and H % 8 == 0 and I % 8 == 0) else None
-
-        def dW(defer, dy_, x_, gW_, No, Ko, rows, lda, ldb):
-            if defer:
-                group.append((dy_, x_, gW_, No, Ko, rows, lda, ldb, Ko))
-            else:
-                fork()
-                with torch.cuda.stream(side):
-                    self._dW(dy_, x_, gW_, No, Ko, rows, lda=lda, ldb=ldb)
-
         # the deferred layers go in grouped_dw_parts launches; a part is launched (on the side stream) behind the attention backward of
         # its last layer, so the main chain's remaining VALU- and HBM-bound kernels still run beside it
         full = [l for l in reversed(range(cfg.layers)) if S["layers"][l]["rows"] == M]
         parts = min(self.grouped_dw_parts or (len(full) + 1) // 2, max(len(full), 1))
         flush_after = {full[(len(full) * (i + 1) + parts - 1) // parts - 1]: i for i in range(parts)} if (group is not None and full) else {}
-
-        def flush(part):
-            # every deferred operand outlives the layer loop: the per-layer scratch of this backward and the activations the forward
-            # kept -- never one of the buffers the loop rewrites layer after layer
-            shared = {t.data_ptr() for t in (dctx, da, dxb[0], dxb[1])} | {self._ws[k].data_ptr() for k in ("bw_dctx_tail", "bw_dx_unperm") if k in self._ws}
-            operands = [t.data_ptr() for q in group for t in q[:3]]
-            assert len(set(operands)) == len(operands) and not (shared & set(operands)), "grouped dW: an operand is not a per-layer buffer"
-            tab = self._dw_group.get(part)
-            if tab is None:
-                tab = self._dw_group[part] = ops.GroupedTN(self.device)
-            tab.set(adt, group)      # rebuilt and uploaded only when a pointer or a row count changed
-            wb = tab.workspace_bytes()
-            tab.launch(ws=self._gemm_workspace(wb // 4) if wb else None, alpha=us)
-            group.clear()
-
-        dctx = self._buf("bw_dctx", (M, H), adt)
-        delta = self._buf("bw_delta", (B, A, Lq), torch.float32)
-        da = self._buf("bw_da", (M, H), adt)
-        dxb = [self._buf("bw_dx0", (M, H), adt), self._buf("bw_dx1", (M, H), adt)]
-        M_all = M
+        bw = _Backward(main, side, bucket_hook, group, flush_after, dctx=self._buf("bw_dctx", (M, H), adt),
+                       delta=self._buf("bw_delta", (S["B"], cfg.heads, S["L"]), torch.float32), da=self._buf("bw_da", (M, H), adt),
+                       dxb=(self._buf("bw_dx0", (M, H), adt), self._buf("bw_dx1", (M, H), adt)))
+        dy = S["dhidden"]
         for l in reversed(range(cfg.layers)):
-            p = f"enc.encoder.layer.{l}."
-            a_ = S["layers"][l]
-            phase(f"backward.layer{l}")
-            Wqkv, _, gWqkv, gbqkv = self.qkv_views(l)
-            # the last layer's per-row part ran on the consumed rows only (encoder_forward, tail_rows): so does its backward
-            tail = a_["rows"] != M_all
-            M = a_["rows"]
-            # with dropout the projection branch sees dpre * mask / (1-p) while the residual branch sees dpre itself
-            dpre2 = self._buf(f"bw_dpre2_{l}", (M, H), adt)
-            dprd2 = self._buf(f"bw_dprd2_{l}", (M, H), adt) if pd > 0 else None
-            dpre1 = self._buf(f"bw_dpre1_{l}", (M, H), adt)
-            dprd1 = self._buf(f"bw_dprd1_{l}", (M, H), adt) if pd > 0 else None
-            dz = self._buf(f"bw_dz_{l}", (M, I), adt)
-            dqkv = self._buf(f"bw_dqkv_{l}", (M_all, 3 * H), adt)
-            # LN2 backward (+ bias grad of output.dense)
-            ops.layernorm_bwd(dy, a_["pre2"], a_["mean2"], a_["rstd2"], self.p[p + "output.LayerNorm.weight"], dpre2,
-                              g[p + "output.LayerNorm.weight"], g[p + "output.LayerNorm.bias"], g[p + "output.dense.bias"], M, H,
-                              dx_drop=dprd2, p_drop=pd, drop_key=dk[(self.SITE_OUT2, l)], unscale=us)
-            dproj2 = dprd2 if dprd2 is not None else dpre2
-            defer = group is not None and not tail
-            dW(defer, dproj2, a_["i"], g[p + "output.dense.weight"], H, I, M, H, I)
-            # FFN-up bias gradient without a second pass over dz: the dz GEMM leaves partial column sums (one row per 128-row tile
-            # half) that one small kernel folds (MV_FUSED_COLSUM=0: the column-sum kernel).  The same for dqkv from the attention
-            # backward was built and measured slower (profiles/r03_notes.txt): +80 us on the two kernels for 11 us saved.
-            dz_part = None
-            # (mv_gemm takes the 256x256 MFMA kernel for wide outputs that fill the chip: the same test as in mv_gemm.hip)
-            if use_w2t and mfma_on and M >= 256 and I >= 1024 and I % 256 == 0 and ((M + 255) // 256) * ((I + 127) // 128) >= 128:
-                dz_part = self._buf(f"bw_dzpart_{l}", (2 * ((M + 255) // 256), I), torch.float32)
-            if use_w2t:
-                ops.gemm(dproj2, self._w2t[l], dz, M=M, N=I, K=H, epi=EPI_MUL, r=a_["dgelu"], colsum_part=dz_part)
-            else:
-                ops.gemm(dproj2, self.w[p + "output.dense.weight"], dz, tb=True, M=M, N=I, K=H, epi=EPI_MUL, r=a_["dgelu"])
-            fork()
-            with torch.cuda.stream(side):
-                if dz_part is not None:
-                    ops.colsum_partials(dz_part, dz_part.shape[0], I, I, g[p + "intermediate.dense.bias"], unscale=us)
-                else:
-                    ops.colsum(dz, I, M, I, g[p + "intermediate.dense.bias"], accumulate=True, unscale=us)
-                if defer:
-                    group.append((dz, a_["a"], g[p + "intermediate.dense.weight"], I, H, M, I, H, H))
-                else:
-                    self._dW(dz, a_["a"], g[p + "intermediate.dense.weight"], I, H, M, lda=I, ldb=H)
-            ops.gemm(dz, self.w[p + "intermediate.dense.weight"], da, tb=True, M=M, N=H, K=I, epi=EPI_RES, r=dpre2)
-            # LN1 backward (+ bias grad of attention.output.dense)
-            ops.layernorm_bwd(da, a_["pre1"], a_["mean1"], a_["rstd1"], self.p[p + "attention.output.LayerNorm.weight"], dpre1,
-                              g[p + "attention.output.LayerNorm.weight"], g[p + "attention.output.LayerNorm.bias"],
-                              g[p + "attention.output.dense.bias"], M, H, dx_drop=dprd1, p_drop=pd,
-                              drop_key=dk[(self.SITE_OUT1, l)], unscale=us)
-            dproj1 = dprd1 if dprd1 is not None else dpre1
-            dW(defer, dproj1, a_["ctx_tail"] if tail else a_["ctx"], g[p + "attention.output.dense.weight"], H, H, M, H, H)
-            if tail:
-                # d(ctx) exists on the consumed rows only: everywhere else it is exactly zero
-                dctx_s = self._buf("bw_dctx_tail", (M, H), adt)
-                ops.gemm(dproj1, self.w[p + "attention.output.dense.weight"], dctx_s, tb=True, M=M, N=H, K=H)
-                dctx.zero_()
-                ops.scatter_rows(dctx_s, H, S["sel"] if S["tq"] is None else S["tq"][3], M, H, dctx, H, accumulate=False)
-            else:
-                ops.gemm(dproj1, self.w[p + "attention.output.dense.weight"], dctx, tb=True, M=M, N=H, K=H)
-            M = M_all
-            tq = S["tq"] if tail else None
-            ops.attn_bwd(a_["qkv"], a_["ctx"], dctx, a_["lse"], S["bits"], S["tinfo"], dqkv, delta, B, Lq, A, dh, cu=S["cu"],
-                         total_rows=M, p_drop=pd, dropbits=a_["dropbits"], qlim=tq[2] if tq is not None else None)
-            fork()
-            with torch.cuda.stream(side):
-                ops.colsum(dqkv, 3 * H, M, 3 * H, gbqkv, accumulate=True, unscale=us)
-                if defer:
-                    group.append((dqkv, a_["x"], gWqkv, 3 * H, H, M, 3 * H, H, H))
-                    if l in flush_after:
-                        flush(flush_after[l])
-                else:
-                    self._dW(dqkv, a_["x"], gWqkv, 3 * H, H, M, lda=3 * H, ldb=H)
-                ev_layer = side_done()
-            dx = dxb[l & 1]          # never the buffer dy currently lives in
-            if tail:
-                # the residual branch's gradient (dpre1) also lives on the consumed rows only
-                ops.gemm(dqkv, Wqkv, dx, tb=True, M=M, N=H, K=3 * H)
-                ops.scatter_rows(dpre1, H, S["sel"] if tq is None else tq[3], a_["rows"], H, dx, H, accumulate=True)
-                if tq is not None:         # back to the row order of the layers below
-                    dxu = self._buf("bw_dx_unperm", (M, H), adt)
-                    ops.scatter_rows(dx, H, tq[0], M, H, dxu, H, accumulate=False)
-                    dx = dxu
-            else:
-                ops.gemm(dqkv, Wqkv, dx, tb=True, M=M, N=H, K=3 * H, epi=EPI_RES, r=dpre1)
-            dy = dx
-            if bucket_hook:
-                # LayerNorm / bias gradients of the layer were written on the main stream, the weights on the side stream
-                bucket_hook(f"layer{l}", ev_layer)
+            dy = self._layer_backward(l, dy, bw)
         e = "enc.txt_embeddings."
         phase("backward.embed")
+        B, N, T, D, g, us = S["B"], S["N"], S["T"], cfg.img_hidden, self.g, self.unscale_dev
         dimg = self._buf("bw_dimg", (B * N, H), adt)
-        if getattr(self, "_dE_ev", None) is not None:
+        if self._dE_ev is not None:
             main.wait_event(self._dE_ev)      # the decoder's word-embedding gradient (written, not accumulated) is in place
             self._dE_ev = None
         ops.embed_bwd(self.dt, dy, self._ws["pre0"][:M * H].view(M, H), self._ws["mean0"][:M], self._ws["rstd0"][:M],
                       self.p[e + "LayerNorm.weight"], S["cls_tok"], S["txt"], S["segment"], S["img_pos"], S["sep_tok"],
                       g[e + "word_embeddings.weight"], g[e + "position_embeddings.weight"], g[e + "token_type_embeddings.weight"],
                       g[e + "LayerNorm.weight"], g[e + "LayerNorm.bias"], dimg, B, N, T, H, cfg.vocab_size, cfg.max_pos,
-                      pad_token_id=0, p_drop=pd, drop_key=dk[(self.SITE_EMB, 0)], rowmap=S["rowmap"], n_rows=M, unscale=us,
-                      p_drop_img=S["p_drop_img"])
+                      pad_token_id=0, p_drop=S["p_drop"], drop_key=S["drop_keys"][(self.SITE_EMB, 0)], rowmap=S["rowmap"], n_rows=M,
+                      unscale=us, p_drop_img=S["p_drop_img"])
         main.wait_stream(side)              # every weight gradient is final; the split-K workspace is ours again
         if N > 0:
             ops.colsum(dimg, H, B * N, H, g["enc.img_embeddings.img_embeddings.bias"], accumulate=True, unscale=us)
@@ -1085,6 +979,117 @@ class Engine:
         if bucket_hook:
             bucket_hook("embeddings", None)
         phase(None)
+
+    def _layer_dW(self, bw, defer, dy, x, gW, No, Ko, rows, forked=False):
+        """A layer's weight gradient gW[No, Ko] = dy[rows, No]^T . x[rows, Ko]: queued for the grouped launch (`defer`), else launched on
+        the side stream, behind a fork unless the caller has already made one (`forked`)."""
+        if defer:
+            return bw.group.append((dy, x, gW, No, Ko, rows, No, Ko, Ko))
+        if not forked:
+            self._fork(bw.main, bw.side)
+        with torch.cuda.stream(bw.side):
+            self._dW(dy, x, gW, No, Ko, rows, lda=No, ldb=Ko)
+
+    def _flush_dw_group(self, bw, part):
+        """Launch the queued weight gradients as grouped launch `part` on the current (side) stream."""
+        # every deferred operand outlives the layer loop: the per-layer scratch of this backward and the activations the forward
+        # kept -- never one of the buffers the loop rewrites layer after layer
+        shared = {t.data_ptr() for t in (bw.dctx, bw.da, *bw.dxb)} | {self._ws[k].data_ptr() for k in ("bw_dctx_tail", "bw_dx_unperm") if k in self._ws}
+        operands = [t.data_ptr() for q in bw.group for t in q[:3]]
+        assert len(set(operands)) == len(operands) and not (shared & set(operands)), "grouped dW: an operand is not a per-layer buffer"
+        tab = self._dw_group.get(part)
+        if tab is None:
+            tab = self._dw_group[part] = ops.GroupedTN(self.device)
+        tab.set(self.adt, bw.group)      # rebuilt and uploaded only when a pointer or a row count changed
+        wb = tab.workspace_bytes()
+        tab.launch(ws=self._gemm_workspace(wb // 4) if wb else None, alpha=self.unscale_dev)
+        bw.group.clear()
+
+    def _layer_backward(self, l, dy, bw):
+        """dy = d(output of layer l) -> d(its input).  M: every row; R: the rows its per-row part ran on (encoder_forward, tail_rows)."""
+        cfg, S, adt, g, us = self.cfg, self.S, self.adt, self.g, self.unscale_dev
+        H, A, I = cfg.hidden, cfg.heads, cfg.intermediate
+        B, Lq, M = S["B"], S["L"], S["M"]
+        pd, dk = S["p_drop"], S["drop_keys"]
+        p = f"enc.encoder.layer.{l}."
+        a_ = S["layers"][l]
+        phase(f"backward.layer{l}")
+        Wqkv, _, gWqkv, gbqkv = self.qkv_views(l)
+        R = a_["rows"]
+        tail = R != M
+        # with dropout the projection branch sees dpre * mask / (1-p) while the residual branch sees dpre itself
+        dpre2 = self._buf(f"bw_dpre2_{l}", (R, H), adt)
+        dprd2 = self._buf(f"bw_dprd2_{l}", (R, H), adt) if pd > 0 else None
+        dpre1 = self._buf(f"bw_dpre1_{l}", (R, H), adt)
+        dprd1 = self._buf(f"bw_dprd1_{l}", (R, H), adt) if pd > 0 else None
+        dz = self._buf(f"bw_dz_{l}", (R, I), adt)
+        dqkv = self._buf(f"bw_dqkv_{l}", (M, 3 * H), adt)
+        dctx, delta, da, dx = bw.dctx, bw.delta, bw.da, bw.dxb[l & 1]          # (dx: never the buffer dy currently lives in)
+        # LN2 backward (+ bias grad of output.dense)
+        ops.layernorm_bwd(dy, a_["pre2"], a_["mean2"], a_["rstd2"], self.p[p + "output.LayerNorm.weight"], dpre2,
+                          g[p + "output.LayerNorm.weight"], g[p + "output.LayerNorm.bias"], g[p + "output.dense.bias"], R, H,
+                          dx_drop=dprd2, p_drop=pd, drop_key=dk[(self.SITE_OUT2, l)], unscale=us)
+        dproj2 = dprd2 if dprd2 is not None else dpre2
+        defer = bw.group is not None and not tail
+        self._layer_dW(bw, defer, dproj2, a_["i"], g[p + "output.dense.weight"], H, I, R)
+        # FFN-up bias gradient without a second pass over dz: the dz GEMM leaves partial column sums (one row per 128-row tile
+        # half) that one small kernel folds (MV_FUSED_COLSUM=0: the column-sum kernel).  The same for dqkv from the attention
+        # backward was built and measured slower (profiles/r03_notes.txt): +80 us on the two kernels for 11 us saved.
+        dz_part = None
+        use_w2t = self.dz_nt and self.is16
+        mfma_on = self.fused_colsum and self.is16 and ops.get_impl() == 0       # partial column sums exist in the MFMA kernels only
+        # (mv_gemm takes the 256x256 MFMA kernel for wide outputs that fill the chip: the same test as in mv_gemm.hip)
+        if use_w2t and mfma_on and R >= 256 and I >= 1024 and I % 256 == 0 and ((R + 255) // 256) * ((I + 127) // 128) >= 128:
+            dz_part = self._buf(f"bw_dzpart_{l}", (2 * ((R + 255) // 256), I), torch.float32)
+        if use_w2t:
+            ops.gemm(dproj2, self._w2t[l], dz, M=R, N=I, K=H, epi=EPI_MUL, r=a_["dgelu"], colsum_part=dz_part)
+        else:
+            ops.gemm(dproj2, self.w[p + "output.dense.weight"], dz, tb=True, M=R, N=I, K=H, epi=EPI_MUL, r=a_["dgelu"])
+        self._fork(bw.main, bw.side)
+        with torch.cuda.stream(bw.side):
+            if dz_part is not None:
+                ops.colsum_partials(dz_part, dz_part.shape[0], I, I, g[p + "intermediate.dense.bias"], unscale=us)
+            else:
+                ops.colsum(dz, I, R, I, g[p + "intermediate.dense.bias"], accumulate=True, unscale=us)
+            self._layer_dW(bw, defer, dz, a_["a"], g[p + "intermediate.dense.weight"], I, H, R, forked=True)
+        ops.gemm(dz, self.w[p + "intermediate.dense.weight"], da, tb=True, M=R, N=H, K=I, epi=EPI_RES, r=dpre2)
+        # LN1 backward (+ bias grad of attention.output.dense)
+        ops.layernorm_bwd(da, a_["pre1"], a_["mean1"], a_["rstd1"], self.p[p + "attention.output.LayerNorm.weight"], dpre1,
+                          g[p + "attention.output.LayerNorm.weight"], g[p + "attention.output.LayerNorm.bias"],
+                          g[p + "attention.output.dense.bias"], R, H, dx_drop=dprd1, p_drop=pd,
+                          drop_key=dk[(self.SITE_OUT1, l)], unscale=us)
+        dproj1 = dprd1 if dprd1 is not None else dpre1
+        self._layer_dW(bw, defer, dproj1, a_["ctx_tail"] if tail else a_["ctx"], g[p + "attention.output.dense.weight"], H, H, R)
+        dctx_r = self._buf("bw_dctx_tail", (R, H), adt) if tail else dctx
+        ops.gemm(dproj1, self.w[p + "attention.output.dense.weight"], dctx_r, tb=True, M=R, N=H, K=H)
+        if tail:
+            # d(ctx) exists on the consumed rows only: everywhere else it is exactly zero
+            dctx.zero_()
+            ops.scatter_rows(dctx_r, H, S["tail_sel"], R, H, dctx, H, accumulate=False)
+        tq = S["tq"] if tail else None
+        ops.attn_bwd(a_["qkv"], a_["ctx"], dctx, a_["lse"], S["bits"], S["tinfo"], dqkv, delta, B, Lq, A, H // A, cu=S["cu"],
+                     total_rows=M, p_drop=pd, dropbits=a_["dropbits"], qlim=tq.qlim if tq is not None else None)
+        self._fork(bw.main, bw.side)
+        with torch.cuda.stream(bw.side):
+            ops.colsum(dqkv, 3 * H, M, 3 * H, gbqkv, accumulate=True, unscale=us)
+            self._layer_dW(bw, defer, dqkv, a_["x"], gWqkv, 3 * H, H, M, forked=True)
+            if defer and l in bw.flush_after:
+                self._flush_dw_group(bw, bw.flush_after[l])
+            ev_layer = self._done(bw.side)
+        if tail:
+            # the residual branch's gradient (dpre1) also lives on the consumed rows only
+            ops.gemm(dqkv, Wqkv, dx, tb=True, M=M, N=H, K=3 * H)
+            ops.scatter_rows(dpre1, H, S["tail_sel"], R, H, dx, H, accumulate=True)
+            if tq is not None:         # back to the row order of the layers below
+                dxu = self._buf("bw_dx_unperm", (M, H), adt)
+                ops.scatter_rows(dx, H, tq.perm, M, H, dxu, H, accumulate=False)
+                dx = dxu
+        else:
+            ops.gemm(dqkv, Wqkv, dx, tb=True, M=M, N=H, K=3 * H, epi=EPI_RES, r=dpre1)
+        if bw.hook:
+            # LayerNorm / bias gradients of the layer were written on the main stream, the weights on the side stream
+            bw.hook(f"layer{l}", ev_layer)
+        return dx
 
     # ------------------------------------------------------------------ optimizer
     def check_overflow(self):
@@ -1112,7 +1117,7 @@ class Engine:
         self.ensure_opt()
         phase("optimizer")
         scaler_state = self.scaler if (use_scaler and self.scaler is not None) else None
-        if not (overlap and self.device.type == "cuda" and os.environ.get("MV_SINGLE_STREAM") != "1"):
+        if not (overlap and self.device.type == "cuda") or self.side_stream() == torch.cuda.current_stream():
             self.wait_optimizer()
             ops.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.shadow, self.n_flat, lr, betas[0], betas[1], eps,
                            weight_decay, step, correct_bias, grad_scale, shadow_f16=self.shadow_f, scaler_state=scaler_state)
@@ -1126,9 +1131,6 @@ class Engine:
         main, side = torch.cuda.current_stream(), self.side_stream()
         side.wait_stream(main)                  # gradients (and their all-reduce, which the caller finished) are final
         evs = {}
-        use_w2t = self.dz_nt and self.is16
-        if use_w2t and self._w2t is None:
-            self._w2t = [torch.empty((cfg.intermediate, cfg.hidden), dtype=self.adt, device=self.device) for _ in range(cfg.layers)]
         # the embeddings range in two kernels: the small tables / LayerNorm / image projection first (the next forward's first GEMM reads the
         # image projection), then the word table (110 us of HBM traffic that this GEMM no longer waits for)
         word_end = self.layout["enc.txt_embeddings.position_embeddings.weight"][0]
@@ -1142,12 +1144,9 @@ class Engine:
                                None if self.shadow is None else self.shadow[sl], e_ - s_, lr, betas[0], betas[1], eps,
                                weight_decay, step, correct_bias, grad_scale,
                                shadow_f16=None if self.shadow_f is None else self.shadow_f[sl], scaler_state=scaler_state)
-                if use_w2t and name.startswith("layer"):
-                    l = int(name[5:])
-                    ops.transpose(self.w[f"enc.encoder.layer.{l}.output.dense.weight"], self._w2t[l], cfg.hidden, cfg.intermediate)
-                ev = torch.cuda.Event()
-                ev.record(side)
-                evs[name] = ev
+                if self.dz_nt and self.is16 and name.startswith("layer"):
+                    self._w2t_fill(int(name[5:]))
+                evs[name] = self._done(side)
         self._opt_ev = evs
         self._w2t_ev, self._w2t_stale = evs["heads"], False
         self.shadow_dirty = False

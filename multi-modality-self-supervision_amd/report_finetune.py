@@ -154,7 +154,7 @@ class CXRBertForReportFinetune(TaskModel):
         ops.lm_loss_bwd(sv["logits"], d["row_ptr"], d["labels"], d["weights"], d["sample"], self.label_smoothing, sv["row_stat"],
                         sv["keep"], sv["inv"], gd, dl, U=U, V=V, ld=sv["Vp"], ldd=sv["Vp"], loss_scale_dev=eng.loss_scale_dev)
         dxr = eng._mlm_backward(dl, "rf_")
-        dhid = eng.S["dhidden"] = eng._buf("dhidden_tail", (U + B, H), eng.adt)
+        dhid = eng.dhidden_buffer()
         dhid[:U].copy_(dxr)
         dhid[U:].zero_()                         # the B first rows: the pooler / ITM / sequence-relationship heads receive nothing
         eng.encoder_backward()

@@ -146,7 +146,7 @@ class CXRBertForRetrieval(TaskModel):
         scratch = eng._buf("ret_ce_scratch", (3,), torch.float32)
         scratch.zero_()
         ops.ce_fwd_bwd(logits, 2, labels, B, 2, scratch, d8, 8, grad_scale_dev=gs, loss_scale_dev=eng.loss_scale_dev)
-        eng.S["dhidden"] = eng._buf("dhidden_tail", (B, H), eng.adt)      # the compact final state's gradient: the pooler path fills it
+        eng.dhidden_buffer()                                              # the compact final state's gradient: the pooler path fills it
         eng._itm_backward(d8)
         eng.encoder_backward()
 

@@ -92,14 +92,12 @@ class TrainStep:
         zero_ev = None
         if train:
             # the flat gradient is cleared on the engine's side stream, which is idle during the forward; the heads wait for it
-            main = torch.cuda.current_stream() if eng.device.type == "cuda" else None
-            side = eng.side_stream() if main is not None else None
-            if side is not None and side is not main:
-                side.wait_stream(main)                 # behind the previous step's optimizer (it read the gradients)
+            if eng.device.type == "cuda":
+                side = eng.side_stream()
+                side.wait_stream(torch.cuda.current_stream())      # behind the previous step's optimizer (it read the gradients)
                 with torch.cuda.stream(side):
                     eng.flat_g.zero_()
-                    zero_ev = torch.cuda.Event()
-                    zero_ev.record(side)
+                    zero_ev = eng._done(side)
             else:
                 eng.flat_g.zero_()
         desc = batch.get("attn_desc") if use_desc else None

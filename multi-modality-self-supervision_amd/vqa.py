@@ -188,9 +188,8 @@ class CXRBertForVQA(FlatHead):
         ops.dact(2, dh1, acts["h1"], dz, B * 2 * H)
         ops.colsum(dz, 2 * H, B, 2 * H, gb1, accumulate=True, unscale=us)
         eng._dW(dz, acts["x"], gW1, 2 * H, H, B, lda=2 * H, ldb=H)
-        dx = eng._buf("dhidden_tail", (B, H), adt)
+        dx = eng.dhidden_buffer()                 # the compact final state's gradient: the pooler / ITM / MLM heads get none
         ops.gemm(dz, self._view(w, HEAD_KEYS[0]), dx, tb=True, M=B, N=H, K=2 * H, lda=2 * H, ldb=H)
-        eng.S["dhidden"] = dx                     # the compact final state's gradient: the pooler / ITM / MLM heads get none
         eng.encoder_backward()
 
     def forward(self, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, ans_labels=None, ans_type=None, vqa_inference=False):

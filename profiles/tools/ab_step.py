@@ -29,20 +29,10 @@ def timed(n=8):
 
 VARIANTS = {
     "pack": [("padded", lambda: setattr(step, "pack_rows", False)), ("packed", lambda: setattr(step, "pack_rows", True))],
-    "dwsplit": [("dW split-K auto (fills 256 CUs)", lambda: setattr(model.engine, "dw_splitk", 0)),
-                ("dW split-K <= 4", lambda: setattr(model.engine, "dw_splitk", 4)),
-                ("dW split-K <= 3", lambda: setattr(model.engine, "dw_splitk", 3)),
-                ("dW split-K <= 2", lambda: setattr(model.engine, "dw_splitk", 2))],
     "lnin": [("LayerNorm inputs fp32", lambda: setattr(model.engine, "ln_in_16", False)),
              ("LayerNorm inputs f16", lambda: setattr(model.engine, "ln_in_16", True))],
     "dznt": [("dz on the 128x128 kernel over W2 as stored", lambda: setattr(model.engine, "dz_nt", False)),
              ("dz on the 256-row kernel over a W2^T copy", lambda: setattr(model.engine, "dz_nt", True))],
-    "dwo": [("small dW: at most 16 split-K slabs", lambda: setattr(model.engine, "dw_splitk", 16)),
-            ("small dW: up to 32 slabs (auto)", lambda: setattr(model.engine, "dw_splitk", 0))],
-    "headk": [("decoder input gradient: one pass over K = 30,522", lambda: setattr(model.engine, "head_splitk", False)),
-              ("decoder input gradient: split-K", lambda: setattr(model.engine, "head_splitk", True))],
-    "dEside": [("decoder weight gradient on the main stream", lambda: setattr(model.engine, "head_on_side", False)),
-               ("decoder weight gradient on the side stream", lambda: setattr(model.engine, "head_on_side", True))],
     "optov": [("AdamW on the main stream after the backward", lambda: setattr(step, "overlap_optimizer", False)),
               ("AdamW on the side stream under the next forward", lambda: setattr(step, "overlap_optimizer", True))],
     "fcs": [("FFN-up bias gradient: column-sum kernel over dz", lambda: setattr(model.engine, "fused_colsum", False)),
@@ -54,14 +44,6 @@ VARIANTS = {
            ("prefetch, 8 waves x 512 blocks", lambda: mv.hip_ops.set_rowops_variant(0)),
            ("prefetch, 16 waves x 256 blocks", lambda: mv.hip_ops.set_rowops_variant(3)),
            ("prefetch, 4 waves x 512 blocks", lambda: mv.hip_ops.set_rowops_variant(2 | (512 << 8)))],
-    "optwait": [("forward waits for the optimizer's first kernel before its preparation kernels", lambda: setattr(model.engine, "late_opt_wait", False)),
-                ("... right before the first reader of the embeddings range", lambda: setattr(model.engine, "late_opt_wait", True))],
-    "hps": [("MLM head's bias / transform parameter gradients on the main chain", lambda: setattr(model.engine, "head_params_on_side", False)),
-            ("... on the side stream", lambda: setattr(model.engine, "head_params_on_side", True))],
-    "itm": [("ITM head after the MLM head on the main stream", lambda: setattr(model.engine, "itm_on_side", False)),
-            ("ITM head on the side stream under the decoder GEMM", lambda: setattr(model.engine, "itm_on_side", True))],
-    "logits": [("MLM logits f32", lambda: setattr(model.engine, "logits_16", False)),
-               ("MLM logits in the forward encoding (f16)", lambda: setattr(model.engine, "logits_16", True))],
     "tq": [("last layer's attention: every row a query", lambda: setattr(model.engine, "tail_queries", False)),
            ("consumed rows only as queries (reordered rows, qlim)", lambda: setattr(model.engine, "tail_queries", True))],
     "rounds": [("ring tile height: rounds 1-4's choice (128x128 kernel for 768-column outputs)", lambda: mv.hip_ops.set_gemm_rounds(0)),

@@ -1,4 +1,5 @@
-"""MLM head forward (transform + LayerNorm + tied decoder) and the loss kernel at the step's shape, f32 against f16 logits.
+"""MLM head forward (transform + LayerNorm + tied decoder) and the loss kernel at the step's shape.  (The f16-logits arm this tool
+once compared went with Engine.logits_16; profiles/r03_notes.txt keeps its figures.)
 usage: python profiles/tools/heads_time.py"""
 import os
 import sys
@@ -29,11 +30,10 @@ def t_of(fn, reps=10):
     for _ in range(reps): fn()
     e1.record(); e1.synchronize()
     return e0.elapsed_time(e1) / reps * 1e3
-for flag in (False, True):
-    logits = eng._mlm_forward(xr, xr_b, R, "ht_", logits16=flag)
-    Vp = logits.shape[1]
-    dl = torch.empty((R, Vp), dtype=eng.adt, device=dev)
-    stats = torch.zeros(6, device=dev)
-    tf = t_of(lambda: eng._mlm_forward(xr, xr_b, R, "ht_", logits16=flag))
-    tc = t_of(lambda: ops.ce_fwd_bwd(logits, Vp, lab, R, V, stats[0:3], dl, Vp, grad_scale=1.0 / R, loss_scale_dev=eng.loss_scale_dev))
-    print(f"logits16={flag}: R={R} logits dtype {logits.dtype}: transform+LN+decoder {tf:.1f} us, CE {tc:.1f} us")
+logits = eng._mlm_forward(xr, xr_b, R, "ht_")
+Vp = logits.shape[1]
+dl = torch.empty((R, Vp), dtype=eng.adt, device=dev)
+stats = torch.zeros(6, device=dev)
+tf = t_of(lambda: eng._mlm_forward(xr, xr_b, R, "ht_"))
+tc = t_of(lambda: ops.ce_fwd_bwd(logits, Vp, lab, R, V, stats[0:3], dl, Vp, grad_scale=1.0 / R, loss_scale_dev=eng.loss_scale_dev))
+print(f"R={R} logits dtype {logits.dtype}: transform+LN+decoder {tf:.1f} us, CE {tc:.1f} us")

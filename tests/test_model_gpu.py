@@ -1373,3 +1373,37 @@ def test_f16_operands_survive_outlier_channels(gop):
         m16.engine.wait_optimizer()
         torch.cuda.synchronize()
         assert torch.equal(m16.engine.flat_p, p_before)
+
+
+def test_single_stream_switch_runs_the_same_step_on_one_stream(monkeypatch):
+    """MV_SINGLE_STREAM=1 puts everything the engine's side stream carries on the current stream.  The model and batch
+    of tests/test_gemm_grouped_gpu.py::_step -- packed ragged rows, dropout on, one tail layer, two grouped layers: the smallest step that
+    enters every side-stream block -- must compute the same step either way, by that file's bounds for "same path, other launch order"
+    (loss sums and LayerNorm / bias gradients are f32 atomics: two runs of one path already differ in the last bits)."""
+    from tests.test_gemm_grouped_gpu import same_loss
+
+    def step(single):
+        if single:
+            monkeypatch.setenv("MV_SINGLE_STREAM", "1")
+        else:
+            monkeypatch.delenv("MV_SINGLE_STREAM", raising=False)
+        cfg = mv.ModelConfig(hidden=128, heads=2, intermediate=512, layers=3, vocab_size=1024, max_pos=512, dropout=0.1)
+        b = mv.data.synthetic_batch(cfg.vocab_size, 4, 6, 56, "full", seed=41, device=DEV, lengths=[56, 17, 40, 3])
+        torch.manual_seed(77)
+        model = mv.CXRBERT(cfg, None, dtype=torch.bfloat16, device=DEV)
+        model.reset_parameters(seed=6)
+        model.train()
+        eng = model.engine
+        stats = mv.TrainStep(model, lr=0.0)(dict(b), train=True).cpu()
+        torch.cuda.synchronize()
+        S = eng.S
+        assert S["cu"] is not None and S["p_drop"] == pytest.approx(0.1) and S["layers"][-1]["rows"] < S["M"]
+        assert sum(t.launches for t in eng._dw_group.values()) == 1 and [a["rows"] for a in S["layers"][:2]] == [S["M"]] * 2
+        assert (eng.side_stream() == torch.cuda.current_stream()) == single
+        return stats, {k: v.clone() for k, v in eng.g.items()}
+
+    s1, g1 = step(True)
+    s0, g0 = step(False)
+    same_loss(s1, s0)
+    for k in g0:
+        assert float((g1[k] - g0[k]).norm()) <= 3e-3 * float(g0[k].norm()), k
