@@ -419,7 +419,12 @@ int mv_cast(const void* src, int src_dtype, void* dst, int dst_dtype, size_t n, 
  *                     running_mean / running_var (unbiased variance) when they are given (both or neither)
  *   mv_bn_act       : y = (x - mean) * rstd * gamma + beta (+ residual) (max 0 when relu != 0); C % 4 == 0; x may be f32
  *                     while y / residual are bf16
- *   mv_maxpool3x3s2 : 3x3 / stride 2 / pad 1 max pooling, NHWC                                                      */
+ *   mv_maxpool3x3s2 : 3x3 / stride 2 / pad 1 max pooling, NHWC; C % 4 == 0
+ * Alignment: mv_col_stats, mv_bn_act and mv_maxpool3x3s2 move four elements per access, so x, y and residual must be aligned to
+ * four of their elements (8 bytes of bf16, 16 of f32) and mean / rstd / gamma / beta to 16 bytes: MV_E_SHAPE otherwise.
+ * mv_im2col takes any element-aligned base (it gathers element by element unless both bases are 16-byte aligned), and so does
+ * mv_nchw_to_nhwc.  Null pointers and non-positive sizes, Cp < C: MV_E_ARG; ldk < kh*kw*C, an output size that is not positive,
+ * C or ldx not a multiple of 4: MV_E_SHAPE; MV_F16, or f32 y from bf16 x: MV_E_DTYPE.  A refused call writes nothing.      */
 int mv_nchw_to_nhwc(const float* src, void* dst, int dst_dtype, int B, int C, int H, int W, int Cp, void* stream);
 int mv_im2col(int dtype, const void* src, int B, int H, int W, int C, int kh, int kw, int stride, int pad, void* dst, int ldk,
               void* stream);

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const TX* __restrict__ x, c
   }
 }
 
-// 3x3 / stride 2 / pad 1 max pooling over NHWC (torchvision ResNet stem), 8 channels per thread
+// 3x3 / stride 2 / pad 1 max pooling over NHWC (torchvision ResNet stem), 4 channels per thread
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const T* __restrict__ x, T* __restrict__ y, int B, int H, int W, int C,
                                                            int Ho, int Wo) {
@@ -165,6 +165,9 @@ inline int grid_for(size_t n, int per_block = 256, int cap = 16384) {
   size_t b = (n + per_block - 1) / per_block;
   return (int)(b < 1 ? 1 : (b > (size_t)cap ? cap : b));
 }
+
+// ld4 / st4 move four elements in one access (8 bytes of bf16, 16 of f32): the base must be aligned to that
+inline bool aligned4(const void* p, int dtype) { return (((uintptr_t)p) & (dtype == MV_F32 ? 15 : 7)) == 0; }
 
 }  // namespace
 
@@ -202,6 +205,8 @@ extern "C" int mv_col_stats(int dtype, const void* x, int ldx, int rows, int C, 
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !stats || rows <= 0 || C <= 0 || ldx < C) return MV_E_ARG;
   if ((C & 3) || (ldx & 3)) return MV_E_SHAPE;
+  if (dtype != MV_BF16 && dtype != MV_F32) return MV_E_DTYPE;      // before the memset: a refused call leaves stats alone
+  if (!aligned4(x, dtype)) return MV_E_SHAPE;
   hipError_t e = hipMemsetAsync(stats, 0, sizeof(float) * 2 * (size_t)C, stream);
   if (e != hipSuccess) return (int)e;
   int slabs = (rows + 511) / 512;
@@ -230,6 +235,10 @@ extern "C" int mv_bn_act(int dtype, const void* x, int x_dtype, const float* mea
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !mean || !rstd || !gamma || !beta || !y || rows <= 0 || C <= 0) return MV_E_ARG;
   if (C & 3) return MV_E_SHAPE;
+  if (!((dtype == MV_BF16 && (x_dtype == MV_BF16 || x_dtype == MV_F32)) || (dtype == MV_F32 && x_dtype == MV_F32))) return MV_E_DTYPE;
+  if (!aligned4(x, x_dtype) || !aligned4(y, dtype) || !aligned4(residual, dtype) || !aligned4(mean, MV_F32) || !aligned4(rstd, MV_F32) ||
+      !aligned4(gamma, MV_F32) || !aligned4(beta, MV_F32))
+    return MV_E_SHAPE;
   const size_t n = (size_t)rows * (C / 4);
   if (dtype == MV_BF16 && x_dtype == MV_BF16) bn_act_kernel<bf16_t, bf16_t><<<grid_for(n), 256, 0, stream>>>((const bf16_t*)x, mean, rstd, gamma, beta, (const bf16_t*)residual, (bf16_t*)y, (size_t)rows, C, relu);
   else if (dtype == MV_BF16 && x_dtype == MV_F32) bn_act_kernel<float, bf16_t><<<grid_for(n), 256, 0, stream>>>((const float*)x, mean, rstd, gamma, beta, (const bf16_t*)residual, (bf16_t*)y, (size_t)rows, C, relu);
@@ -243,6 +252,8 @@ extern "C" int mv_maxpool3x3s2(int dtype, const void* x, void* y, int B, int H, 
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0) return MV_E_ARG;
   if (C & 3) return MV_E_SHAPE;
+  if (dtype != MV_BF16 && dtype != MV_F32) return MV_E_DTYPE;
+  if (!aligned4(x, dtype) || !aligned4(y, dtype)) return MV_E_SHAPE;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const size_t n = (size_t)B * Ho * Wo * (C / 4);
   if (dtype == MV_BF16) maxpool3x3s2_kernel<bf16_t><<<grid_for(n), 256, 0, stream>>>((const bf16_t*)x, (bf16_t*)y, B, H, W, C, Ho, Wo);

@@ -161,6 +161,77 @@ def test_rowop_rejects(lib):
     assert lib.mv_count_nonfinite(None, 16, P, None) == E_ARG
 
 
+def test_region_encoder_support_rejects(lib):
+    """csrc/mv_conv.hip: one assertion per documented condition of the six entry points (include/medvill.h).  The outputs are real,
+    NaN-filled host buffers, compared afterwards: a refused call has written nothing, mv_col_stats' clearing of `stats` included."""
+    def nan(n):                              # 64-byte aligned, whatever the allocator returns
+        raw = np.empty(n * 4 + 64, dtype=np.uint8)
+        a = raw[(-raw.ctypes.data) % 64:][:n * 4].view(np.float32)
+        a[...] = np.nan
+        return a
+    dst, cols, stats, mean, rstd, rmean, rvar, y, pooled = (nan(256) for _ in range(9))
+    outs = (dst, cols, stats, mean, rstd, rmean, rvar, y, pooled)
+    before = [o.copy() for o in outs]
+    ptr = lambda a: a.ctypes.data
+
+    def nhwc(src=P, dst_=None, dt=BF16, B=1, C_=3, H=2, W=2, Cp=8):
+        return lib.mv_nchw_to_nhwc(src, ptr(dst) if dst_ is None else dst_, dt, B, C_, H, W, Cp, None)
+    assert nhwc(src=None) == E_ARG and lib.mv_nchw_to_nhwc(P, None, BF16, 1, 3, 2, 2, 8, None) == E_ARG
+    for k in ("B", "C_", "H", "W"):
+        assert nhwc(**{k: 0}) == E_ARG and nhwc(**{k: -1}) == E_ARG, k
+    assert nhwc(Cp=2) == E_ARG and nhwc(Cp=0) == E_ARG                     # Cp < C
+    assert nhwc(dt=F16) == E_DTYPE and nhwc(dt=3) == E_DTYPE
+
+    def im2col(dt=BF16, src=P, B=1, H=4, W=4, C_=8, kh=3, kw=3, s=1, p=1, dst_=None, ldk=72):
+        return lib.mv_im2col(dt, src, B, H, W, C_, kh, kw, s, p, ptr(cols) if dst_ is None else dst_, ldk, None)
+    assert im2col(src=None) == E_ARG and lib.mv_im2col(BF16, P, 1, 4, 4, 8, 3, 3, 1, 1, None, 72, None) == E_ARG
+    for k in ("B", "H", "W", "C_", "kh", "kw", "s"):
+        assert im2col(**{k: 0}) == E_ARG and im2col(**{k: -2}) == E_ARG, k
+    assert im2col(p=-1) == E_ARG
+    assert im2col(ldk=71) == E_SHAPE and im2col(ldk=64) == E_SHAPE         # ldk < kh*kw*C
+    assert im2col(H=2, W=2, kh=7, kw=7, p=1, ldk=392) == E_SHAPE           # an output size that is not positive
+    assert im2col(W=1, kw=3, p=0) == E_SHAPE
+    assert im2col(dt=F16) == E_DTYPE and im2col(dt=-1) == E_DTYPE
+
+    def col_stats(dt=BF16, x=P, ldx=8, rows=4, C_=8, st=None):
+        return lib.mv_col_stats(dt, x, ldx, rows, C_, ptr(stats) if st is None else st, None)
+    assert col_stats(x=None) == E_ARG and lib.mv_col_stats(BF16, P, 8, 4, 8, None, None) == E_ARG
+    assert col_stats(rows=0) == E_ARG and col_stats(rows=-4) == E_ARG and col_stats(C_=0) == E_ARG and col_stats(ldx=4) == E_ARG
+    assert col_stats(C_=6) == E_SHAPE and col_stats(ldx=10) == E_SHAPE     # C % 4, ldx % 4
+    assert col_stats(dt=F16) == E_DTYPE and col_stats(dt=5) == E_DTYPE     # and `stats` is not cleared on the way out
+    assert col_stats(x=P + 4) == E_SHAPE and col_stats(x=P + 2) == E_SHAPE and col_stats(dt=F32, x=P + 8) == E_SHAPE      # four elements
+
+    def fin(st=P, C_=8, rows=4, mean_=None, rstd_=None, rm=None, rv=None):
+        return lib.mv_bn_finalize(st, C_, rows, 1e-5, 0.1, ptr(mean) if mean_ is None else mean_, ptr(rstd) if rstd_ is None else rstd_, rm, rv, None)
+    assert fin(st=None) == E_ARG and fin(C_=0) == E_ARG and fin(C_=-8) == E_ARG and fin(rows=0) == E_ARG and fin(rows=-1) == E_ARG
+    assert lib.mv_bn_finalize(P, 8, 4, 1e-5, 0.1, None, ptr(rstd), None, None, None) == E_ARG
+    assert lib.mv_bn_finalize(P, 8, 4, 1e-5, 0.1, ptr(mean), None, None, None, None) == E_ARG
+    assert fin(rm=ptr(rmean)) == E_ARG and fin(rv=ptr(rvar)) == E_ARG      # only one of the two running buffers
+
+    def act(dt=BF16, x=P, xdt=BF16, mean_=P, rstd_=P, gamma=P, beta=P, res=None, y_=None, rows=4, C_=8, use_y=True):
+        return lib.mv_bn_act(dt, x, xdt, mean_, rstd_, gamma, beta, res, (ptr(y) if y_ is None else y_) if use_y else None, rows, C_, 1, None)
+    for k in ("x", "mean_", "rstd_", "gamma", "beta"):
+        assert act(**{k: None}) == E_ARG, k
+    assert act(use_y=False) == E_ARG and act(rows=0) == E_ARG and act(rows=-3) == E_ARG and act(C_=0) == E_ARG
+    assert act(C_=6) == E_SHAPE                                            # C % 4
+    assert act(dt=F32, xdt=BF16) == E_DTYPE                                # f32 out from bf16 in: no such body
+    assert act(dt=F16, xdt=F16) == E_DTYPE and act(dt=BF16, xdt=F16) == E_DTYPE and act(dt=F16, xdt=F32) == E_DTYPE and act(dt=4) == E_DTYPE
+    assert act(x=P + 4) == E_SHAPE and act(xdt=F32, x=P + 8) == E_SHAPE and act(y_=ptr(y) + 4) == E_SHAPE and act(res=P + 2) == E_SHAPE
+    assert act(dt=F32, xdt=F32, y_=ptr(y) + 8) == E_SHAPE and act(dt=F32, xdt=F32, res=P + 8) == E_SHAPE
+    for k in ("mean_", "rstd_", "gamma", "beta"):
+        assert act(**{k: P + 8}) == E_SHAPE and act(**{k: P + 4}) == E_SHAPE, k
+
+    def pool(dt=BF16, x=P, y_=None, B=1, H=4, W=4, C_=8, use_y=True):
+        return lib.mv_maxpool3x3s2(dt, x, (ptr(pooled) if y_ is None else y_) if use_y else None, B, H, W, C_, None)
+    assert pool(x=None) == E_ARG and pool(use_y=False) == E_ARG
+    for k in ("B", "H", "W", "C_"):
+        assert pool(**{k: 0}) == E_ARG and pool(**{k: -1}) == E_ARG, k
+    assert pool(C_=6) == E_SHAPE and pool(dt=F16) == E_DTYPE and pool(dt=9) == E_DTYPE
+    assert pool(x=P + 4) == E_SHAPE and pool(y_=ptr(pooled) + 4) == E_SHAPE and pool(dt=F32, x=P + 8) == E_SHAPE and pool(dt=F32, y_=ptr(pooled) + 8) == E_SHAPE
+    for o, b in zip(outs, before):
+        assert o.tobytes() == b.tobytes()
+
+
 def test_decode_rejects(lib):
     """mv_decode.hip: one assertion per documented condition; every call returns before a launch."""
     gr = lambda **k: lib.mv_gemm_rows(k.get("dt", BF16), k.get("M", 16), k.get("N", 64), k.get("K", 64), k.get("x", P), k.get("ldx", 64), k.get("W", P),
