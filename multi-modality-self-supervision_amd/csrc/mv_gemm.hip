@@ -25,6 +25,7 @@
 #define GT_BN 128
 #define GT_BK 64
 #define GT_STAGE_BYTES 32768   // A tile 16 KiB + B tile 16 KiB
+static_assert(GT_BM == T128 && GT_BN == T128 && GT_BK == T128_BK && GT_STAGE_BYTES == MFMA128_STAGE_BYTES, "mv_gemm_plan.h plans for this tile");
 
 template <bool TR>
 __device__ __forceinline__ void stage_load(u32x4 (&reg)[4], __amdgpu_buffer_rsrc_t rs, unsigned bytes, int ld,
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(256, SB ? 3 : 2) void gemm_mfma_kernel(GemmArgs p) 
       fast[j] = p.vec_ok && (p.N - n >= 4);                                                                   \
       b4[j] = (f32x4){0.f, 0.f, 0.f, 0.f}; rc[j] = b4[j]; rn[j] = b4[j];                                      \
       if (fast[j]) {                                                                                          \
-        if (E_ == MV_EPI_BIAS || E_ == MV_EPI_BIAS_GELU || E_ == MV_EPI_BIAS_RES || E_ == MV_EPI_BIAS_TANH || E_ == MV_EPI_BIAS_GELU_D || E_ == MV_EPI_BIAS_RELU || E_ == MV_EPI_BIAS_RES_RELU)    \
+        if (mv_epi_has_bias(E_))                                                                              \
           b4[j] = *(const f32x4*)(p.bias + n);                                                                \
         rc[j] = epi_load_res4<E_>(p, m0 + wm + l15, n);                                                       \
       }                                                                                                       \
@@ -337,22 +338,14 @@ __global__ void splitk_reduce_kernel(GemmArgs p) {
 
 // ------------------------------------------------------------------------------------------
 // test / experiment hooks (constants in the product library: mv_common.h)
-#define g_mv_gemm_force (mv_knob(MV_KNOB_GEMM_FORCE))        // 0 auto, 1 force the 128x128 kernel, 2 force the 256-row kernel
-#define g_mv_gemm_nj (mv_knob(MV_KNOB_GEMM_NJ))              // 0 auto, kernel variant
 #define g_mv_gemm_dbg (mv_knob(MV_KNOB_GEMM_DBG))
-#define g_mv_persistent_cus (mv_knob(MV_KNOB_PERSISTENT_CUS))
 
 static inline bool aligned_to(const void* p, size_t a) { return p == nullptr || (((uintptr_t)p) % a) == 0; }
 
-// Which kernel serves a 16-bit MFMA product and how many split-K slabs it would like when the caller leaves the choice to the library
-// (splitk = 0) -- ONE definition, used by mv_gemm itself and by mv_gemm_workspace_bytes / mv_workspace_bytes, so that a host that is not
-// hip_ops.py can size the workspace without re-deriving this from the source.
-struct GemmRoute {
-  bool big;            // the 256-row ring kernels (else the 128x128 kernel)
-  int variant;         // ring variant: 14 = 256x256x64 two stages, 24 = its persistent form, 2 = 256x128, 10 = 320x256 (one round)
-  long long tiles;     // output tiles of the chosen kernel
-  long long sk_auto;   // split-K slabs wanted at splitk = 0 with an unlimited workspace (1 = none)
-};
+// what mv_gemm_plan (mv_gemm_plan.h) is not allowed to ask for itself: the knob values and the CU count
+static MvGemmKnobs gemm_knobs() {
+  return {g_mv_impl, mv_knob(MV_KNOB_GEMM_FORCE), mv_knob(MV_KNOB_GEMM_NJ), mv_knob(MV_KNOB_GEMM_ROUNDS), mv_knob(MV_KNOB_PERSISTENT_CUS)};
+}
 static int gemm_n_cu() {
   static const int n = [] {
     int dev = 0, v = 0;
@@ -362,65 +355,14 @@ static int gemm_n_cu() {
   }();
   return n;
 }
-static GemmRoute gemm_route(int ta, int tb, int M, int N, int K, int splitk, bool f16, bool rows256 = false) {      // rows256: the caller needs 256-row tiles (fused column sums)
-  GemmRoute r;
-  const int tm2 = (M + 255) / 256;
-  const long long t256 = (long long)tm2 * ((N + 255) / 256), t128 = (long long)tm2 * ((N + 127) / 128);
-  // measured on the model's shapes (profiles/r01_gemm_variants.txt): the ring kernels win for y = x.W^T with wide outputs and for
-  // dW = dy^T.x, the 128x128 register-staged kernel for dx = dy.W and for 768-column outputs (three blocks per CU), also for long contractions
-  const bool wide_nt = !ta && !tb && N >= 1024;
-  r.big = (g_mv_gemm_force == 2) || (g_mv_gemm_force == 0 && M >= 256 && N >= 128 && ((K & 7) == 0 || (ta && tb)) && (wide_nt || ta) &&
-                                     (t128 >= 128 || (K >= 4096 && splitk != 1)));
-  r.variant = 0;
-  r.sk_auto = 1;
-  // WHOLE ROUNDS of tiles (round 5).  y = x.W^T and dx = dy.W with narrow outputs (768 columns: attention output projection, FFN-down and
-  // the three input gradients of a layer) over ~25,500 packed rows are 300 tiles of 256 x 256 -- 1.17 rounds of the 256 CUs, the second one
-  // 44 tiles on an idle chip -- and 1,200 tiles of 128 x 128 = 1.56 rounds of that kernel's 768 slots; as 320 x 256 tiles they are 240 tiles:
-  // ONE round with 94 % of the CUs busy.  That is wave quantisation, not kernel quality (a tile takes the same time whether 44 or 256 CUs
-  // are busy), so the tile shape is chosen per call by (whole rounds) x (time of one round of that kernel).
-  // Measured at 25,483 rows (profiles/r05_notes.txt): FFN-down 151 -> 112 us, da 156 -> 113, dx(qkv) 117 -> 87, Wo 50 -> 42, dctx 44 -> 34.
-  const bool rounds_on = mv_knob(MV_KNOB_GEMM_ROUNDS) != 0 && g_mv_gemm_force == 0 && g_mv_gemm_nj == 0;
-  if (rounds_on && !ta && !r.big && splitk <= 1 && M >= 2048 && N >= 256 && (N & 7) == 0 && (K & 7) == 0 && K >= 256) {
-    // whole rounds x the measured time of one round (any K: the three kernels' rounds scale alike): 128 x 128 tiles on 768 slots 75,
-    // 256 x 256 ring tiles on 256 CUs 85, 320 x 256 ring tiles 112 (FFN-down shape, us).  A partly filled round costs a full one.
-    const int n_cu = gemm_n_cu();
-    const long long tn = (N + 255) / 256, t320 = (long long)((M + 319) / 320) * tn;
-    const long long s128 = (long long)((M + GT_BM - 1) / GT_BM) * ((N + GT_BN - 1) / GT_BN);
-    const long long c128 = ((s128 + 3 * n_cu - 1) / (3 * n_cu)) * 75, c256 = ((t256 + n_cu - 1) / n_cu) * 85,
-                    c320 = rows256 ? (1ll << 60) : ((t320 + n_cu - 1) / n_cu) * 112;
-    if (c256 < c128 && c256 <= c320) { r.big = true; r.variant = 14; r.tiles = t256; return r; }
-    if (c320 < c128 && c320 < c256) { r.big = true; r.variant = 10; r.tiles = t320; return r; }
-  }
-  // Wide y = x.W^T outputs run several rounds of tiles; the last one is partly empty.  320-row tiles when they take strictly less
-  // (rounds x rows): the fused QKV projection at 25,483 rows is 900 tiles of 256 rows = 4 rounds (3.52 full) or 720 of 320 = 3 rounds.
-  if (rounds_on && r.big && !ta && !tb && !rows256 && splitk <= 1 && (K & 7) == 0) {
-    const int n_cu = gemm_n_cu();
-    const long long tn = (N + 255) / 256, t320 = (long long)((M + 319) / 320) * tn;
-    const long long c256 = ((t256 + n_cu - 1) / n_cu) * 8, c320 = ((t320 + n_cu - 1) / n_cu) * 10;
-    if (c320 < c256) { r.variant = 10; r.tiles = t320; return r; }
-  }
-  if (r.big) {
-    // 256x256 with 64-deep stages (whole 128-B lines per LDS-DMA row): best measured.  Weight gradients (split-K units, f32 partial
-    // tiles) gain 5-8 % from the persistent form; y = x.W^T does not (profiles/r01_gemm_variants.txt)
-    r.variant = g_mv_gemm_nj ? g_mv_gemm_nj : (ta ? 24 : 14);        // (knob: 14, 24, 10 = 320-row tiles or 2 = 256x128 tiles, 4 waves, two blocks per CU)
-    if (r.variant == 10 && ta) r.variant = 24;                      // the 320-row form exists for y = x.W^T and dx = dy.W
-    if (r.variant == 2 && !(f16 && ta == tb)) r.variant = ta ? 24 : 14;   // the 256x128 form exists for f16 operands of y = x.W^T and dW = dy^T.x
-    const bool v128 = r.variant == 2;
-    r.tiles = v128 ? t128 : (r.variant == 10 ? (long long)((M + 319) / 320) * ((N + 255) / 256) : t256);
-    const long long slots = v128 ? 512 : 256;
-    // enough slabs to give every CU a unit, each at least 1024 deep; at most 32
-    if (r.variant != 10 && r.tiles < slots && K >= 2048) { long long sk = slots / r.tiles; if (sk > K / 1024) sk = K / 1024; if (sk > 32) sk = 32; if (sk < 1) sk = 1; r.sk_auto = sk; }
-  } else {
-    r.tiles = (long long)((M + GT_BM - 1) / GT_BM) * ((N + GT_BN - 1) / GT_BN);
-    if (r.tiles < 512 && K >= 2048) { long long sk = 768 / r.tiles; if (sk > K / 1024) sk = K / 1024; if (sk > 16) sk = 16; if (sk < 1) sk = 1; r.sk_auto = sk; }
-  }
-  return r;
-}
 
+// The split-K slabs a 16-bit product would like when the caller leaves the choice to the library (splitk = 0) come from the same plan
+// mv_gemm runs, so that a host that is not hip_ops.py can size the workspace without re-deriving this from the source.
 extern "C" size_t mv_gemm_workspace_bytes(int dtype, int ta, int tb, int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0 || !mv_is16(dtype) || g_mv_impl != 0) return 0;      // split-K is chosen on the MFMA kernels only
-  const GemmRoute r = gemm_route(ta, tb, M, N, K, 0, dtype == MV_F16);
-  return r.sk_auto > 1 ? (size_t)r.sk_auto * (size_t)M * (size_t)N * sizeof(float) : 0;
+  MvGemmCall c = {};
+  c.dtype = dtype; c.ta = ta; c.tb = tb; c.M = M; c.N = N; c.K = K; c.c_dtype = MV_F32; c.operands_ok = 1;      // splitk = 0, no workspace yet
+  const MvGemmPlan plan = mv_gemm_plan(c, gemm_knobs(), gemm_n_cu());      // sk_auto is 1 off the MFMA kernels and for a call without a shape
+  return plan.sk_auto > 1 ? (size_t)plan.sk_auto * (size_t)M * (size_t)N * sizeof(float) : 0;
 }
 
 extern "C" size_t mv_workspace_bytes(int hidden, int intermediate, int vocab, int img_hidden, int max_rows, int max_label_rows, int max_regions) {
@@ -441,6 +383,16 @@ extern "C" size_t mv_workspace_bytes(int hidden, int intermediate, int vocab, in
   return w;
 }
 
+// the 128x128 kernel of one operand layout: two stages, or one stage (f16-encoded operands: always; y = x.W^T, dx = dy.W and dW = dy^T.x)
+template <bool TA, bool TB>
+static void launch_mfma128(const MvGemmPlan& plan, bool f16, dim3 grid, dim3 block, hipStream_t stream, const GemmArgs& p) {
+  if (f16) {
+    if constexpr (!(TA && !TB)) mv_launch_lds<gemm_mfma_kernel<TA, TB, false, true, true>>(grid, block, plan.lds_bytes, stream, p);
+  }
+  else if (plan.kernel == MV_GEMM_MFMA128_2STAGE) mv_launch_lds<gemm_mfma_kernel<TA, TB>>(grid, block, plan.lds_bytes, stream, p);
+  else mv_launch_lds<gemm_mfma_kernel<TA, TB, false, true>>(grid, block, plan.lds_bytes, stream, p);
+}
+
 extern "C" int mv_gemm(int dtype, int ta, int tb, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
                        void* C, int ldc, int c_dtype, const float* bias, int epi, const void* R, int ldr, int r_dtype,
                        void* C2, int ldc2, void* C3, int ldc3, int c3_dtype, int splitk, float* ws, size_t ws_bytes,
@@ -451,39 +403,29 @@ extern "C" int mv_gemm(int dtype, int ta, int tb, int M, int N, int K, const voi
   if (!mv_dtype_ok(dtype) || !mv_dtype_ok(c_dtype)) return MV_E_DTYPE;
   if (C3 && (!mv_is16(c3_dtype) || ldc3 < N)) return MV_E_DTYPE;
   if (epi < 0 || epi > MV_EPI_BIAS_RES_RELU) return MV_E_ARG;
-  const bool need_bias = (epi == MV_EPI_BIAS || epi == MV_EPI_BIAS_GELU || epi == MV_EPI_BIAS_RES || epi == MV_EPI_BIAS_TANH || epi == MV_EPI_BIAS_GELU_D || epi == MV_EPI_BIAS_RELU || epi == MV_EPI_BIAS_RES_RELU);
-  const bool need_r = (epi == MV_EPI_BIAS_RES || epi == MV_EPI_DGELU || epi == MV_EPI_RES || epi == MV_EPI_MUL || epi == MV_EPI_BIAS_RES_RELU);
+  const bool need_bias = mv_epi_has_bias(epi), need_r = mv_epi_has_r(epi), need_c2 = mv_epi_has_c2(epi);
   if (need_bias && !bias) return MV_E_ARG;
   if (need_r && (!R || !mv_dtype_ok(r_dtype))) return MV_E_ARG;
-  if ((epi == MV_EPI_BIAS_GELU || epi == MV_EPI_BIAS_GELU_D) && !C2) return MV_E_ARG;
+  if (need_c2 && !C2) return MV_E_ARG;
   if (lda < (ta ? M : K) || ldb < (tb ? N : K) || ldc < N) return MV_E_SHAPE;
   if (need_r && ldr < N) return MV_E_SHAPE;
-  if (splitk < 0) splitk = 1;
-  if (splitk > 1 || accumulate) {
-    if (epi != MV_EPI_NONE || c_dtype != MV_F32 || C3) return MV_E_SHAPE;
-  }
-  if (splitk > 1) {
-    if (!ws || ws_bytes < (size_t)splitk * M * N * sizeof(float)) return MV_E_WORKSPACE;
-  }
-  if (alpha_dev && (epi != MV_EPI_NONE || c_dtype != MV_F32 || C3)) return MV_E_ARG;
-  if (splitk == 0 && (!mv_is16(dtype) || g_mv_impl != 0)) splitk = 1;   // auto split-K only on the MFMA kernels
+  // everything the plan needs to know about the pointers
   GemmArgs p;
   p.A = A; p.B = B; p.C = C; p.C2 = C2; p.bias = bias; p.R = R; p.C3 = C3;
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldc2 = ldc2; p.ldr = ldr; p.ldc3 = ldc3;
   p.c_dtype = c_dtype; p.r_dtype = r_dtype; p.c3_dtype = c3_dtype; p.epi = epi; p.accumulate = accumulate;
-  p.splitk = splitk; p.ws = ws; p.dbg = g_mv_gemm_dbg; p.alpha = alpha_dev; p.csum = colsum_part;
+  p.ws = ws; p.dbg = g_mv_gemm_dbg; p.alpha = alpha_dev; p.csum = colsum_part;
   p.drop = mv_make_drop(epi == MV_EPI_BIAS_RES ? p_drop : 0.f, drop_key);
-  if (p.drop.thr && (N & 3)) return MV_E_SHAPE;   // the mask is keyed on groups of 4 consecutive columns
   const size_t csz = (c_dtype == MV_F32) ? 16 : 8;
   const size_t rsz = (r_dtype == MV_F32) ? 16 : 8;
   p.vec_ok = ((ldc & 3) == 0) && aligned_to(C, csz) && (!C3 || (((ldc3 & 3) == 0) && aligned_to(C3, 8))) &&
              (!need_bias || aligned_to(bias, 16)) &&
              (!need_r || (((ldr & 3) == 0) && aligned_to(R, rsz))) &&
-             ((epi != MV_EPI_BIAS_GELU && epi != MV_EPI_BIAS_GELU_D) || (((ldc2 & 3) == 0) && aligned_to(C2, csz)));
+             (!need_c2 || (((ldc2 & 3) == 0) && aligned_to(C2, csz)));
   p.r8_ok = need_r && mv_is16(r_dtype) && ((ldr & 7) == 0) && aligned_to(R, 16);
   p.vec8_ok = mv_is16(c_dtype) && ((ldc & 7) == 0) && aligned_to(C, 16) && (!need_bias || aligned_to(bias, 16)) &&
               (!C3 || (((ldc3 & 7) == 0) && aligned_to(C3, 16))) &&
-              ((epi != MV_EPI_BIAS_GELU && epi != MV_EPI_BIAS_GELU_D) || (((ldc2 & 7) == 0) && aligned_to(C2, 16)));
+              (!need_c2 || (((ldc2 & 7) == 0) && aligned_to(C2, 16)));
   // (N itself need not be a multiple of anything: the 16-byte path covers whole 64-column strips only, the ragged last strip of e.g. the
   //  30,522-column decoder takes the per-lane path)
   {   // the 16-byte-store epilogue addresses its outputs through buffer descriptors: sizes below 2 GiB, else the 8-byte path
@@ -491,122 +433,44 @@ extern "C" int mv_gemm(int dtype, int ta, int tb, int M, int N, int K, const voi
     if (bC >= 0x7fffffffULL || bC2 >= 0x7fffffffULL || bC3 >= 0x7fffffffULL) p.vec8_ok = 0;
     p.bytesC = (unsigned)bC; p.bytesC2 = (unsigned)bC2; p.bytesC3 = (unsigned)bC3;
   }
-  const bool mfma = mv_is16(dtype) && (g_mv_impl == 0);
+  // the MFMA kernels read their operands through buffer descriptors in 16-byte pieces
+  const size_t bytesA = ((size_t)((ta ? K : M) - 1) * lda + (size_t)(((ta ? M : K) + 7) & ~7)) * 2;
+  const size_t bytesB = ((size_t)((tb ? K : N) - 1) * ldb + (size_t)(((tb ? N : K) + 7) & ~7)) * 2;
+  p.bytesA = (unsigned)bytesA; p.bytesB = (unsigned)bytesB;
+
+  MvGemmCall c = {};
+  c.dtype = dtype; c.ta = ta; c.tb = tb; c.M = M; c.N = N; c.K = K; c.splitk = splitk; c.ws_bytes = ws_bytes; c.has_ws = ws != nullptr;
+  c.epi = epi; c.c_dtype = c_dtype; c.accumulate = accumulate; c.has_c3 = C3 != nullptr; c.has_colsum = colsum_part != nullptr;
+  c.vec8_ok = p.vec8_ok; c.r8_ok = p.r8_ok; c.has_alpha = alpha_dev != nullptr; c.drop_on = p.drop.thr != 0;
+  c.operands_ok = !(lda & 7) && !(ldb & 7) && aligned_to(A, 16) && aligned_to(B, 16) && bytesA < 0x7fffffffULL && bytesB < 0x7fffffffULL;
+  const MvGemmPlan plan = mv_gemm_plan(c, gemm_knobs(), gemm_n_cu());
+  if (plan.rc != MV_OK) return plan.rc;
+  p.kchunk = plan.kchunk; p.splitk = plan.splitk;
+
+  const dim3 grid(plan.grid_x, plan.grid_y, plan.grid_z), block(plan.block);
   const bool f16 = dtype == MV_F16;
-  if (mfma && f16 && ta && !tb) return MV_E_DTYPE;    // f16 operands: y = x.W^T, dx = dy.W and dW = dy^T.x
-  if (mfma) {
-    if ((lda & 7) || (ldb & 7) || !aligned_to(A, 16) || !aligned_to(B, 16)) return MV_E_SHAPE;
-    const size_t bytesA = ((size_t)((ta ? K : M) - 1) * lda + (size_t)(((ta ? M : K) + 7) & ~7)) * 2;
-    const size_t bytesB = ((size_t)((tb ? K : N) - 1) * ldb + (size_t)(((tb ? N : K) + 7) & ~7)) * 2;
-    if (bytesA >= 0x7fffffffULL || bytesB >= 0x7fffffffULL) return MV_E_SHAPE;
-    p.bytesA = (unsigned)bytesA; p.bytesB = (unsigned)bytesB;
-    // tile choice (gemm_route): a 256-row ring kernel when it fills the chip, the 128x128 kernel for small problems, dx and 768-column outputs
-    const GemmRoute route = gemm_route(ta, tb, M, N, K, splitk, f16, colsum_part != nullptr);
-    const bool big = route.big;
-    if (big) {
-      const int variant = route.variant;
-      const bool v128 = variant == 2;
-      const long long tiles_v = route.tiles;
-      long long sk = splitk;
-      if (splitk > 1 || splitk == 0) {      // 0 = auto
-        sk = route.sk_auto;
-        if (splitk > 1 && sk > splitk) sk = splitk;
-        if (sk > 1 && ws) { const long long fit = (long long)(ws_bytes / ((size_t)M * N * sizeof(float))); if (sk > fit) sk = fit < 1 ? 1 : fit; }
-        if (sk > 1 && (!ws || epi != MV_EPI_NONE || c_dtype != MV_F32)) sk = 1;
-      }
-      (void)v128;
-      int kchunk = (int)((K + sk - 1) / sk);
-      kchunk = (kchunk + 63) / 64 * 64;
-      p.kchunk = kchunk;
-      p.splitk = splitk = (K + kchunk - 1) / kchunk;
-      // variants: 14 = 256x256 with 64-deep stages x2 (128-B lines), 24 = its persistent form, 2 = 256x128 (32-deep x3, 2 blocks/CU)
-      const int tiles = (int)tiles_v;
-      // fused column sums: only the path that owns whole 64-column strips per wave and stores 16-byte pieces computes them
-      if (colsum_part && !(variant == 14 && splitk == 1 && !accumulate && p.vec8_ok && (N & 255) == 0 && mv_is16(c_dtype) &&
-                           (epi == MV_EPI_NONE || epi == MV_EPI_BIAS || epi == MV_EPI_BIAS_GELU_D || ((epi == MV_EPI_MUL || epi == MV_EPI_RES) && p.r8_ok))))
-        return MV_E_SHAPE;
-      dim3 grid(tiles, splitk);
-      const int n_cu = gemm_n_cu();
-      // persistent kernels: at most g_mv_persistent_cus blocks when the host partitions the chip (mv_set_persistent_cus)
-      const int n_blk = (g_mv_persistent_cus > 0 && g_mv_persistent_cus < n_cu) ? g_mv_persistent_cus : n_cu;
-      const int rc_ring = mv_launch_ring(p, ta, tb, f16, variant, tiles, splitk, n_blk, stream);
+  switch (plan.kernel) {
+    case MV_GEMM_VALU:
+      if (dtype == MV_F32) hipLaunchKernelGGL(gemm_simple_kernel<float>, grid, block, 0, stream, p, ta, tb);
+      else if (f16) hipLaunchKernelGGL(gemm_simple_kernel<f16_t>, grid, block, 0, stream, p, ta, tb);
+      else hipLaunchKernelGGL(gemm_simple_kernel<bf16_t>, grid, block, 0, stream, p, ta, tb);
+      break;
+    // one LDS stage and three blocks per CU by default (10-15 % faster on the model's 768-column GEMMs at ~25k rows:
+    // profiles/r01_gemm_variants.txt); the two-stage form stays reachable for cross-checks (mv_set_gemm_variant(., 32))
+    case MV_GEMM_MFMA128:
+    case MV_GEMM_MFMA128_2STAGE:
+      if (!ta && !tb) launch_mfma128<false, false>(plan, f16, grid, block, stream, p);
+      else if (!ta && tb) launch_mfma128<false, true>(plan, f16, grid, block, stream, p);
+      else if (ta && tb) launch_mfma128<true, true>(plan, f16, grid, block, stream, p);
+      else launch_mfma128<true, false>(plan, f16, grid, block, stream, p);
+      break;
+    default: {   // the 256-row ring kernels: mv_gemm_ring_*.hip
+      const int rc_ring = mv_launch_ring(p, ta, tb, f16, plan, stream);
       if (rc_ring != MV_OK) return rc_ring;
-    } else {
-      if (colsum_part) return MV_E_SHAPE;        // the 256x256 ring kernel only
-      if (splitk == 0) {
-        splitk = 1;
-        if (route.sk_auto > 1 && ws && epi == MV_EPI_NONE && c_dtype == MV_F32) {
-          splitk = (int)route.sk_auto;
-          if (ws_bytes < (size_t)splitk * M * N * sizeof(float)) splitk = 1;
-        }
-      }
-      int kchunk = (K + splitk - 1) / splitk;
-      kchunk = (kchunk + GT_BK - 1) / GT_BK * GT_BK;
-      p.kchunk = kchunk;
-      p.splitk = splitk = (K + kchunk - 1) / kchunk;
-      const int tiles = ((M + GT_BM - 1) / GT_BM) * ((N + GT_BN - 1) / GT_BN);
-      dim3 grid(tiles, splitk), block(256);
-      const size_t shm = 2 * GT_STAGE_BYTES;
-#define LAUNCH_MFMA(TA_, TB_)                                                                              \
-  do {                                                                                                     \
-    static bool attr_set = false;                                                                          \
-    if (!attr_set) {                                                                                       \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_kernel<TA_, TB_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)shm);                                                                 \
-      attr_set = true;                                                                                     \
-    }                                                                                                      \
-    hipLaunchKernelGGL((gemm_mfma_kernel<TA_, TB_>), grid, block, shm, stream, p);                          \
-  } while (0)
-#define LAUNCH_MFMA_SB(TA_, TB_)                                                                           \
-  do {                                                                                                     \
-    static bool attr_sb = false;                                                                           \
-    if (!attr_sb) {                                                                                        \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_kernel<TA_, TB_, false, true>,                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, GT_STAGE_BYTES);               \
-      attr_sb = true;                                                                                      \
-    }                                                                                                      \
-    hipLaunchKernelGGL((gemm_mfma_kernel<TA_, TB_, false, true>), grid, block, GT_STAGE_BYTES, stream, p); \
-  } while (0)
-      // one LDS stage and three blocks per CU by default (10-15 % faster on the model's 768-column GEMMs at ~25k rows:
-      // profiles/r01_gemm_variants.txt); the two-stage form stays reachable for cross-checks (mv_set_gemm_variant(., 32))
-      const bool sb = g_mv_gemm_nj != 32;
-#define LAUNCH_MFMA_H(TA_, TB_)                                                                            \
-  do {                                                                                                     \
-    static bool attr_h = false;                                                                            \
-    if (!attr_h) {                                                                                         \
-      (void)hipFuncSetAttribute((const void*)gemm_mfma_kernel<TA_, TB_, false, true, true>,                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, GT_STAGE_BYTES);               \
-      attr_h = true;                                                                                       \
-    }                                                                                                      \
-    hipLaunchKernelGGL((gemm_mfma_kernel<TA_, TB_, false, true, true>), grid, block, GT_STAGE_BYTES, stream, p); \
-  } while (0)
-      if (f16) {        // f16-encoded operands: always the one-stage form
-        if (!ta && !tb) LAUNCH_MFMA_H(false, false);
-        else if (!ta && tb) LAUNCH_MFMA_H(false, true);
-        else LAUNCH_MFMA_H(true, true);
-      }
-      else if (!ta && !tb) { if (sb) LAUNCH_MFMA_SB(false, false); else LAUNCH_MFMA(false, false); }
-      else if (!ta && tb) { if (sb) LAUNCH_MFMA_SB(false, true); else LAUNCH_MFMA(false, true); }
-      else if (ta && tb) { if (sb) LAUNCH_MFMA_SB(true, true); else LAUNCH_MFMA(true, true); }
-      else { if (sb) LAUNCH_MFMA_SB(true, false); else LAUNCH_MFMA(true, false); }
-#undef LAUNCH_MFMA_H
-#undef LAUNCH_MFMA_SB
-#undef LAUNCH_MFMA
     }
-  } else {
-    if (colsum_part) return MV_E_SHAPE;
-    int kchunk = (K + splitk - 1) / splitk;
-    kchunk = (kchunk + 15) / 16 * 16;
-    p.kchunk = kchunk;
-    p.splitk = splitk = (K + kchunk - 1) / kchunk;
-    dim3 grid((N + 63) / 64, (M + 63) / 64, splitk), block(256);
-    if (grid.y > 65535) return MV_E_SHAPE;
-    if (dtype == MV_F32) hipLaunchKernelGGL(gemm_simple_kernel<float>, grid, block, 0, stream, p, ta, tb);
-    else if (dtype == MV_F16) hipLaunchKernelGGL(gemm_simple_kernel<f16_t>, grid, block, 0, stream, p, ta, tb);
-    else hipLaunchKernelGGL(gemm_simple_kernel<bf16_t>, grid, block, 0, stream, p, ta, tb);
   }
   MV_CHECK_LAUNCH();
-  if (splitk > 1) {
+  if (plan.reduce) {
     const size_t total4 = ((size_t)M * N + 3) / 4;
     int blocks = (int)((total4 + 255) / 256);
     if (blocks > 4096) blocks = 4096;
@@ -621,16 +485,11 @@ extern "C" int mv_gemm(int dtype, int ta, int tb, int M, int N, int K, const voi
 // table, the unit map and the tail rule are plain host code in mv_gemm_group.h; this file only validates and launches.
 int mv_launch_ring_tn_grouped(const MvGroupHeader& h, const GroupArgs& ga, bool f16, int n_blk, hipStream_t stream);    // mv_gemm_ring_tn.hip
 
-static int grouped_blocks() {
-  const int n_cu = gemm_n_cu();
-  return (g_mv_persistent_cus > 0 && g_mv_persistent_cus < n_cu) ? g_mv_persistent_cus : n_cu;
-}
-
 extern "C" size_t mv_gemm_grouped_table_bytes(int count) { return mv_group_table_bytes(count); }
 
 extern "C" int mv_gemm_grouped_fill(int dtype, int count, const mv_group_problem* problems, int n_blocks, void* table_host, size_t table_bytes) {
   if (n_blocks < 0) return MV_E_ARG;
-  return mv_group_fill(dtype, count, problems, n_blocks > 0 ? n_blocks : grouped_blocks(), table_host, table_bytes);
+  return mv_group_fill(dtype, count, problems, n_blocks > 0 ? n_blocks : mv_persistent_blocks(gemm_knobs().persistent_cus, gemm_n_cu()), table_host, table_bytes);
 }
 
 extern "C" size_t mv_gemm_grouped_workspace_bytes(const void* table_host) { return mv_group_workspace_bytes(table_host); }
@@ -657,7 +516,8 @@ extern "C" int mv_gemm_grouped_tn(int dtype, int count, const void* table_host, 
   GroupArgs ga;
   ga.table = table_dev; ga.ws = ws; ga.alpha = alpha_dev; ga.accumulate = accumulate;
   // the plan fixes how the tail is cut for h.n_blocks blocks; any grid computes the same result (a unit's owner is unit mod grid)
-  const int n_blk = h.n_blocks < grouped_blocks() ? h.n_blocks : grouped_blocks();
+  const int n_max = mv_persistent_blocks(gemm_knobs().persistent_cus, gemm_n_cu());
+  const int n_blk = h.n_blocks < n_max ? h.n_blocks : n_max;
   return mv_launch_ring_tn_grouped(h, ga, dtype == MV_F16, n_blk, (hipStream_t)stream_);
 }
 
@@ -696,13 +556,8 @@ extern "C" int mv_conv2d(int dtype, const void* x, const void* w, void* y, int y
   while ((1 << p.cvCshift) < C) ++p.cvCshift;
   const long long tiles = ((rows + GT_BM - 1) / GT_BM) * ((O + GT_BN - 1) / GT_BN);
   if (tiles > 0x7fffffffLL) return MV_E_SHAPE;
-  const size_t shm = GT_STAGE_BYTES;           // one LDS stage, three blocks per CU (see gemm_mfma_kernel)
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_mfma_kernel<false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm_mfma_kernel<false, false, true, true>), dim3((unsigned)tiles, 1), dim3(256), shm, stream, p);
+  // one LDS stage, three blocks per CU (see gemm_mfma_kernel)
+  mv_launch_lds<gemm_mfma_kernel<false, false, true, true>>(dim3((unsigned)tiles, 1), dim3(256), GT_STAGE_BYTES, stream, p);
   MV_CHECK_LAUNCH();
   return MV_OK;
 }

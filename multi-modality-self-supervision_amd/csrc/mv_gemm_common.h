@@ -3,6 +3,7 @@
 // (they compile in parallel).
 #pragma once
 #include "mv_common.h"
+#include "mv_gemm_plan.h"
 
 struct GemmArgs {
   const void* A; const void* B; void* C; void* C2; const float* bias; const void* R;
@@ -28,6 +29,11 @@ struct GemmArgs {
   int cvH, cvW, cvC, cvCshift, cvKw, cvStride, cvPad, cvHo, cvWo;
 };
 
+// epilogue classes: which operands an epilogue reads or writes besides C
+constexpr __host__ __device__ bool mv_epi_has_bias(int e) { return e == MV_EPI_BIAS || e == MV_EPI_BIAS_GELU || e == MV_EPI_BIAS_RES || e == MV_EPI_BIAS_TANH || e == MV_EPI_BIAS_GELU_D || e == MV_EPI_BIAS_RELU || e == MV_EPI_BIAS_RES_RELU; }
+constexpr __host__ __device__ bool mv_epi_has_r(int e) { return e == MV_EPI_BIAS_RES || e == MV_EPI_DGELU || e == MV_EPI_RES || e == MV_EPI_MUL || e == MV_EPI_BIAS_RES_RELU; }
+constexpr __host__ __device__ bool mv_epi_has_c2(int e) { return e == MV_EPI_BIAS_GELU || e == MV_EPI_BIAS_GELU_D; }
+
 // ------------------------------------------------------------------------------------------
 // fused epilogue on 4 consecutive columns (n .. n+3) of row m.
 // Slow path (scalar, run-time epilogue selector): ragged right edge / unaligned leading dimensions.
@@ -41,6 +47,7 @@ __device__ __forceinline__ void epilogue4_slow(const GemmArgs& p, int m, int n, 
     float x = v[i] * al;
     const int e = p.epi;
     float b = 0.f, r = 0.f;
+    // (spelled out, not mv_epi_has_bias / mv_epi_has_r: on the run-time selector the calls change the instruction order of every kernel that inlines this)
     if (e == MV_EPI_BIAS || e == MV_EPI_BIAS_GELU || e == MV_EPI_BIAS_RES || e == MV_EPI_BIAS_TANH || e == MV_EPI_BIAS_GELU_D || e == MV_EPI_BIAS_RELU || e == MV_EPI_BIAS_RES_RELU) b = p.bias[n + i];
     if (e == MV_EPI_BIAS_RES || e == MV_EPI_DGELU || e == MV_EPI_RES || e == MV_EPI_MUL || e == MV_EPI_BIAS_RES_RELU) r = ld_any(p.R, (size_t)m * p.ldr + n + i, p.r_dtype);
     switch (e) {
@@ -86,7 +93,7 @@ template <int E>
 __device__ __forceinline__ f32x4 epi_load_res4(const GemmArgs& p, int m, int n) {
   f32x4 r = {0.f, 0.f, 0.f, 0.f};
   if (m >= p.M) return r;
-  if (E == MV_EPI_BIAS_RES || E == MV_EPI_DGELU || E == MV_EPI_RES || E == MV_EPI_MUL || E == MV_EPI_BIAS_RES_RELU) {
+  if (mv_epi_has_r(E)) {
     const size_t ro = (size_t)m * p.ldr + n;
     r = ld4_any(p.R, ro, p.r_dtype);
   } else if (E == MV_EPI_NONE) {
@@ -100,7 +107,7 @@ __device__ __forceinline__ void epilogue4v(const GemmArgs& p, int m, int n, f32x
   const size_t co = (size_t)m * p.ldc + n;
   f32x4 o = v;
   if (E == MV_EPI_NONE && p.alpha) o *= *p.alpha;
-  if (E == MV_EPI_BIAS || E == MV_EPI_BIAS_GELU || E == MV_EPI_BIAS_RES || E == MV_EPI_BIAS_TANH || E == MV_EPI_BIAS_GELU_D || E == MV_EPI_BIAS_RELU || E == MV_EPI_BIAS_RES_RELU) o += b4;
+  if (mv_epi_has_bias(E)) o += b4;
   if (E == MV_EPI_BIAS_RES && p.drop.thr) o = mv_drop4(o, (size_t)m * p.N + n, p.drop);
   if (E == MV_EPI_DGELU) {
 #pragma unroll
@@ -380,7 +387,7 @@ __device__ __forceinline__ bf16x8 g2_frag(const char* tile, int base, int l15, i
 #define G2_EPI_BODY(E_)                                                                                        \
   {                                                                                                            \
     constexpr int EE = (E_) < 0 ? 0 : (E_);                                                                    \
-    constexpr bool HAS_R = (E_) == MV_EPI_BIAS_RES || (E_) == MV_EPI_RES || (E_) == MV_EPI_MUL || (E_) == MV_EPI_DGELU || (E_) == MV_EPI_BIAS_RES_RELU; \
+    constexpr bool HAS_R = mv_epi_has_r(E_);                                                                   \
     constexpr bool WIDE_E = (E_) == MV_EPI_NONE || (E_) == MV_EPI_BIAS || (E_) == MV_EPI_BIAS_GELU_D;          \
     constexpr bool WIDE_R = (E_) == MV_EPI_MUL || (E_) == MV_EPI_RES || (E_) == MV_EPI_BIAS_RES;      /* 16-bit elementwise operand, 16-byte loads */ \
     if (G2_WIDE_COND(NJ)) G2_EPI_WIDE(E_, G2_NI)                                                                \
@@ -388,8 +395,7 @@ __device__ __forceinline__ bf16x8 g2_frag(const char* tile, int base, int l15, i
     const int ncol = n0 + wn + c4 * 4;                                                                         \
     const bool lane_fast = ((E_) >= 0) && col_on && p.vec_ok && (p.N - ncol >= 4);                             \
     f32x4 b4 = {0.f, 0.f, 0.f, 0.f};                                                                           \
-    if (lane_fast && (EE == MV_EPI_BIAS || EE == MV_EPI_BIAS_GELU || EE == MV_EPI_BIAS_RES || EE == MV_EPI_BIAS_TANH || \
-                      EE == MV_EPI_BIAS_GELU_D || EE == MV_EPI_BIAS_RELU || EE == MV_EPI_BIAS_RES_RELU))                                                               \
+    if (lane_fast && mv_epi_has_bias(EE))                                                                      \
       b4 = *(const f32x4*)(p.bias + ncol);                                                                     \
     if (HAS_R && __all(lane_fast || !col_on)) {                                                                \
       /* residual operand: a tile's worth comes from HBM, so G2_RG 16-row groups of row loads are kept in flight \
@@ -435,17 +441,27 @@ __device__ __forceinline__ bf16x8 g2_frag(const char* tile, int base, int l15, i
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 
-// launchers of the 256-row kernels: one translation unit per operand layout (mv_gemm_ring_{nt,nn,tn,tnn}.hip; they compile
-// in parallel).  variant: 14 = ring 256x256, 64-deep stages x2;  24 = persistent form;  f16: f16-encoded operands
-int mv_launch_ring_nt(const GemmArgs& p, bool f16, int variant, int tiles, int splitk, int n_cu, hipStream_t stream);    // y = x.W^T
-int mv_launch_ring_nn(const GemmArgs& p, bool f16, int variant, int tiles, int splitk, int n_cu, hipStream_t stream);    // dx = dy.W
-int mv_launch_ring_tn(const GemmArgs& p, bool f16, int variant, int tiles, int splitk, int n_cu, hipStream_t stream);    // dW = dy^T.x
-int mv_launch_ring_tnn(const GemmArgs& p, bool f16, int variant, int tiles, int splitk, int n_cu, hipStream_t stream);   // A^T.B^T (bf16 only)
-int mv_launch_ring_tn4(const GemmArgs& p, bool f16, int tiles, int splitk, hipStream_t stream);                           // dW, 32-deep stages x4
-static inline int mv_launch_ring(const GemmArgs& p, int ta, int tb, bool f16, int variant, int tiles, int splitk, int n_cu, hipStream_t stream) {
-  if (variant == 4 && ta && tb) return mv_launch_ring_tn4(p, f16, tiles, splitk, stream);
-  if (!ta && !tb) return mv_launch_ring_nt(p, f16, variant, tiles, splitk, n_cu, stream);
-  if (!ta && tb) return mv_launch_ring_nn(p, f16, variant, tiles, splitk, n_cu, stream);
-  if (ta && tb) return mv_launch_ring_tn(p, f16, variant, tiles, splitk, n_cu, stream);
-  return mv_launch_ring_tnn(p, f16, variant, tiles, splitk, n_cu, stream);
+// Launch of a kernel that uses dynamic LDS.  The kernel is a template argument, so every kernel has its own instantiation and with it
+// its own function-local static: hipFuncAttributeMaxDynamicSharedMemorySize is set once per process and kernel.  (Once per process is
+// not once per device -- DESIGN.md; it is this one line now.)
+template <auto KERNEL, typename... Args>
+inline void mv_launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const Args&... args) {
+  static const hipError_t attr_once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  (void)attr_once;
+  hipLaunchKernelGGL(KERNEL, grid, block, (size_t)lds_bytes, stream, args...);
+}
+
+// launchers of the 256-row kernels: one translation unit per operand layout (mv_gemm_ring_{nt,nn,tn,tnn,tn4}.hip; they compile in
+// parallel).  Each switches on plan.kernel and returns MV_E_ARG for a kernel it has no instantiation of; mv_gemm_plan never asks for one.
+int mv_launch_ring_nt(const GemmArgs& p, bool f16, const MvGemmPlan& plan, hipStream_t stream);    // y = x.W^T
+int mv_launch_ring_nn(const GemmArgs& p, bool f16, const MvGemmPlan& plan, hipStream_t stream);    // dx = dy.W
+int mv_launch_ring_tn(const GemmArgs& p, bool f16, const MvGemmPlan& plan, hipStream_t stream);    // dW = dy^T.x
+int mv_launch_ring_tnn(const GemmArgs& p, bool f16, const MvGemmPlan& plan, hipStream_t stream);   // A^T.B^T (bf16 only)
+int mv_launch_ring_tn4(const GemmArgs& p, bool f16, const MvGemmPlan& plan, hipStream_t stream);   // dW, 32-deep stages x4
+static inline int mv_launch_ring(const GemmArgs& p, int ta, int tb, bool f16, const MvGemmPlan& plan, hipStream_t stream) {
+  if (plan.kernel == MV_GEMM_RING_TN4) return mv_launch_ring_tn4(p, f16, plan, stream);
+  if (!ta && !tb) return mv_launch_ring_nt(p, f16, plan, stream);
+  if (!ta && tb) return mv_launch_ring_nn(p, f16, plan, stream);
+  if (ta && tb) return mv_launch_ring_tn(p, f16, plan, stream);
+  return mv_launch_ring_tnn(p, f16, plan, stream);
 }

@@ -32,7 +32,7 @@ __device__ __forceinline__ void g2_stage_mma_tr(const char* tA, const char* tB, 
 // MI = 16-row accumulator groups per wave: 8 -> the 256-row tile; 10 -> a 320-row tile (2 x 160 rows per wave pair, 160 accumulator registers,
 // 72 KiB stages).  Why 320: an output of 768 columns over ~25,500 packed rows is 300 tiles of 256 x 256 = 1.17 rounds of the 256 CUs (the second
 // round runs 44 tiles on an otherwise idle chip), and 1.56 rounds of 768 slots on the 128 x 128 kernel; as 320 x 256 tiles it is 240 tiles: ONE
-// round with 94 % of the CUs busy (mv_gemm.hip: gemm_route picks the row count that makes a single round).
+// round with 94 % of the CUs busy (mv_gemm_plan.h picks the row count that makes a single round).
 template <bool TA, bool TB, int NJ, int WN, int NSTAGE, int KS, bool F16 = false, int MI = 8>
 __global__ __launch_bounds__(128 * WN, 2) void gemm_ring_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -44,6 +44,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_ring_kernel(GemmArgs p) {
   constexpr int A_BYTES = BM * 64 * KS;
   constexpr int B_BYTES = (BP512 ? 16384 : 8192) * KS;
   constexpr int STAGE = A_BYTES + B_BYTES;
+  static_assert(STAGE == mv_ring_stage_bytes({NJ, WN, NSTAGE, KS, MI}), "the plan sizes the launch's LDS with the same arithmetic");
   constexpr int LPS = (A_BYTES + B_BYTES) / 1024 / NW;   // LDS-DMA instructions per wave per stage
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -200,6 +201,7 @@ __global__ __launch_bounds__(128 * WN, 1) void gemm_pring_kernel(GemmArgs p, int
   constexpr int STAGE = A_BYTES + B_BYTES;
   constexpr int LPS = STAGE / 1024 / NW;
   constexpr int EPI_OPS = 28;                     // lower bound of the VMEM ops a wave issues in a full-tile epilogue (32 stores)
+  static_assert(STAGE == mv_ring_stage_bytes({NJ, WN, NSTAGE, KS, 8}), "the plan sizes the launch's LDS with the same arithmetic");
   static_assert(NW * 4608 <= STAGE, "epilogue scratch must fit in one ring stage");
   static_assert((NSTAGE - 2) * LPS + EPI_OPS < 64, "vmcnt is a 6-bit counter");
   const int tid = threadIdx.x, lane = tid & 63;
@@ -445,28 +447,14 @@ __global__ __launch_bounds__(128 * WN, 1) void gemm_pring_grouped_kernel(GroupAr
   }
 }
 
-#define LAUNCH_PRING(TA_, TB_, NJ_, WN_, NS_, F16_)                                                                 \
-  do {                                                                                                               \
-    constexpr size_t shm = (size_t)(NS_) * 2 * (16384 + ((WN_) * 16 * (NJ_) > 128 ? 16384 : 8192));                  \
-    static bool attr_set = false;                                                                                    \
-    if (!attr_set) {                                                                                                 \
-      (void)hipFuncSetAttribute((const void*)gemm_pring_kernel<TA_, TB_, NJ_, WN_, NS_, F16_>,                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                               \
-      attr_set = true;                                                                                               \
-    }                                                                                                                \
-    const int units = tiles * splitk;                                                                                \
-    hipLaunchKernelGGL((gemm_pring_kernel<TA_, TB_, NJ_, WN_, NS_, F16_>), dim3(units < n_cu ? units : n_cu),        \
-                       dim3(128 * (WN_)), shm, stream, p, units, tiles);                                             \
-  } while (0)
-#define LAUNCH_RING_MI(TA_, TB_, NJ_, WN_, NS_, KS_, F16_, MI_)                                                      \
-  do {                                                                                                               \
-    constexpr size_t shm = (size_t)(NS_) * (KS_) * (2048 * (MI_) + ((WN_) * 16 * (NJ_) > 128 ? 16384 : 8192));        \
-    static bool attr_set = false;                                                                                    \
-    if (!attr_set) {                                                                                                 \
-      (void)hipFuncSetAttribute((const void*)gemm_ring_kernel<TA_, TB_, NJ_, WN_, NS_, KS_, F16_, MI_>,              \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                               \
-      attr_set = true;                                                                                               \
-    }                                                                                                                \
-    hipLaunchKernelGGL((gemm_ring_kernel<TA_, TB_, NJ_, WN_, NS_, KS_, F16_, MI_>), grid, dim3(128 * (WN_)), shm, stream, p); \
-  } while (0)
-#define LAUNCH_RING(TA_, TB_, NJ_, WN_, NS_, KS_, F16_) LAUNCH_RING_MI(TA_, TB_, NJ_, WN_, NS_, KS_, F16_, 8)
+// Launch of the ring kernel a plan names, for one operand layout and encoding.  The template arguments of the instantiation come from
+// mv_ring_shape(KERNEL), the table the plan took the block size and the LDS bytes from; the grid is the plan's.
+template <int KERNEL, bool TA, bool TB, bool F16>
+inline int mv_launch_ring_as(const GemmArgs& p, const MvGemmPlan& plan, hipStream_t stream) {
+  constexpr MvRingShape s = mv_ring_shape(KERNEL);
+  if constexpr (KERNEL == MV_GEMM_PRING)
+    mv_launch_lds<gemm_pring_kernel<TA, TB, s.nj, s.wn, s.nstage, F16>>(dim3(plan.grid_x), dim3(plan.block), plan.lds_bytes, stream, p, plan.units, (int)plan.tiles);
+  else
+    mv_launch_lds<gemm_ring_kernel<TA, TB, s.nj, s.wn, s.nstage, s.ks, F16, s.mi>>(dim3(plan.grid_x, plan.grid_y), dim3(plan.block), plan.lds_bytes, stream, p);
+  return MV_OK;
+}

@@ -1,15 +1,11 @@
 // 256-row LDS-DMA GEMM kernels, operand layout: dx = dy.W (weight contraction-major).  See mv_gemm_ring.h.
 #include "mv_gemm_ring.h"
 
-int mv_launch_ring_nn(const GemmArgs& p, bool f16, int variant, int tiles, int splitk, int n_cu, hipStream_t stream) {
-  dim3 grid(tiles, splitk);
-  if (f16) {
-    if (variant == 10) LAUNCH_RING_MI(false, true, 4, 4, 2, 2, true, 10);               // 320 x 256 tiles (one round of CUs: gemm_route)
-    else LAUNCH_RING(false, true, 4, 4, 2, 2, true);
-  } else {
-    if (variant == 24) LAUNCH_PRING(false, true, 4, 4, 2, false);
-    else if (variant == 10) LAUNCH_RING_MI(false, true, 4, 4, 2, 2, false, 10);
-    else LAUNCH_RING(false, true, 4, 4, 2, 2, false);
+int mv_launch_ring_nn(const GemmArgs& p, bool f16, const MvGemmPlan& plan, hipStream_t stream) {
+  switch (plan.kernel) {
+    case MV_GEMM_RING14: return f16 ? mv_launch_ring_as<MV_GEMM_RING14, false, true, true>(p, plan, stream) : mv_launch_ring_as<MV_GEMM_RING14, false, true, false>(p, plan, stream);
+    case MV_GEMM_RING320: return f16 ? mv_launch_ring_as<MV_GEMM_RING320, false, true, true>(p, plan, stream) : mv_launch_ring_as<MV_GEMM_RING320, false, true, false>(p, plan, stream);
+    case MV_GEMM_PRING: return f16 ? MV_E_ARG : mv_launch_ring_as<MV_GEMM_PRING, false, true, false>(p, plan, stream);
+    default: return MV_E_ARG;
   }
-  return MV_OK;
 }

@@ -1,17 +1,13 @@
 // 256-row LDS-DMA GEMM kernels, operand layout: dW = dy^T.x (both operands contraction-major).  See mv_gemm_ring.h.
 #include "mv_gemm_ring.h"
 
-int mv_launch_ring_tn(const GemmArgs& p, bool f16, int variant, int tiles, int splitk, int n_cu, hipStream_t stream) {
-  dim3 grid(tiles, splitk);
-  if (f16) {
-    if (variant == 2) LAUNCH_RING(true, true, 4, 2, 3, 1, true);
-    else if (variant == 24) LAUNCH_PRING(true, true, 4, 4, 2, true);
-    else LAUNCH_RING(true, true, 4, 4, 2, 2, true);
-  } else {
-    if (variant == 24) LAUNCH_PRING(true, true, 4, 4, 2, false);
-    else LAUNCH_RING(true, true, 4, 4, 2, 2, false);
+int mv_launch_ring_tn(const GemmArgs& p, bool f16, const MvGemmPlan& plan, hipStream_t stream) {
+  switch (plan.kernel) {
+    case MV_GEMM_RING14: return f16 ? mv_launch_ring_as<MV_GEMM_RING14, true, true, true>(p, plan, stream) : mv_launch_ring_as<MV_GEMM_RING14, true, true, false>(p, plan, stream);
+    case MV_GEMM_RING256x128: return f16 ? mv_launch_ring_as<MV_GEMM_RING256x128, true, true, true>(p, plan, stream) : MV_E_ARG;
+    case MV_GEMM_PRING: return f16 ? mv_launch_ring_as<MV_GEMM_PRING, true, true, true>(p, plan, stream) : mv_launch_ring_as<MV_GEMM_PRING, true, true, false>(p, plan, stream);
+    default: return MV_E_ARG;
   }
-  return MV_OK;
 }
 
 // folds the slabs of the tail tiles of a grouped launch into C: block (tail tile, 16-row band), one 16-byte column group per thread
@@ -47,17 +43,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_grouped_kernel(GroupArgs ga
 
 // the grouped launch: `h` is the (validated) host copy of the table's header -- it decides the grid; the kernels read the device copy
 int mv_launch_ring_tn_grouped(const MvGroupHeader& h, const GroupArgs& ga, bool f16, int n_blk, hipStream_t stream) {
-  constexpr size_t shm = (size_t)2 * 2 * (16384 + 16384);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_pring_grouped_kernel<4, 4, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    (void)hipFuncSetAttribute((const void*)gemm_pring_grouped_kernel<4, 4, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    attr_set = true;
-  }
+  constexpr int shm = mv_ring_lds_bytes(MV_GEMM_PRING);
   const int units = h.direct + h.tail * h.split;
   const dim3 grid(units < n_blk ? units : n_blk), block(512);
-  if (f16) hipLaunchKernelGGL((gemm_pring_grouped_kernel<4, 4, 2, true>), grid, block, shm, stream, ga, units);
-  else hipLaunchKernelGGL((gemm_pring_grouped_kernel<4, 4, 2, false>), grid, block, shm, stream, ga, units);
+  if (f16) mv_launch_lds<gemm_pring_grouped_kernel<4, 4, 2, true>>(grid, block, shm, stream, ga, units);
+  else mv_launch_lds<gemm_pring_grouped_kernel<4, 4, 2, false>>(grid, block, shm, stream, ga, units);
   MV_CHECK_LAUNCH();
   if (h.tail > 0) {
     hipLaunchKernelGGL(splitk_reduce_grouped_kernel, dim3(h.tail, MV_GROUP_TILE / 16), dim3(256), 0, stream, ga);

@@ -3,9 +3,9 @@
 // fetch latency that the ring can cover.  See mv_gemm_ring.h.
 #include "mv_gemm_ring.h"
 
-int mv_launch_ring_tn4(const GemmArgs& p, bool f16, int tiles, int splitk, hipStream_t stream) {
-  dim3 grid(tiles, splitk);
-  if (f16) LAUNCH_RING(true, true, 4, 4, 4, 1, true);
-  else LAUNCH_RING(true, true, 4, 4, 4, 1, false);
-  return MV_OK;
+int mv_launch_ring_tn4(const GemmArgs& p, bool f16, const MvGemmPlan& plan, hipStream_t stream) {
+  switch (plan.kernel) {
+    case MV_GEMM_RING_TN4: return f16 ? mv_launch_ring_as<MV_GEMM_RING_TN4, true, true, true>(p, plan, stream) : mv_launch_ring_as<MV_GEMM_RING_TN4, true, true, false>(p, plan, stream);
+    default: return MV_E_ARG;
+  }
 }

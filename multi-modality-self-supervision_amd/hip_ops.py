@@ -409,7 +409,7 @@ def set_rowops_variant(v: int = 0):
 
 
 def set_gemm_rounds(on: int = 1):
-    """1 (default): mv_gemm picks the ring tile height that minimises whole rounds of CUs (csrc/mv_gemm.hip: gemm_route); 0: off."""
+    """1 (default): mv_gemm picks the ring tile height that minimises whole rounds of CUs (csrc/mv_gemm_plan.h: mv_gemm_plan); 0: off."""
     L.set_knob("gemm_rounds", 1 if on else 0)
 
 

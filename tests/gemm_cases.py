@@ -7,7 +7,7 @@ cannot quietly turn one test into a repeat of another.
 
 * every generator returns a dict; the tensors of a case are made from cfg["seed"] alone, so a cfg printed by a failing
   assertion reproduces the case;
-* plan() restates mv_gemm's dispatch (gemm_route, the slab arithmetic, the launchers' variant tables, the epilogue conditions)
+* plan() restates mv_gemm's dispatch (mv_gemm_plan.h: the route, the slab arithmetic, the variant table; and the epilogue conditions)
   with the CU count as a parameter and names everything a case reaches;
 * the references are plain torch in float64 on the already-rounded inputs; none of them calls a kernel of this project;
 * every output element gets its own bound from the arithmetic (no global maximum):
@@ -46,7 +46,7 @@ LAYOUT_OF = {v: k for k, v in LAYOUTS.items()}
 ESIZE = {F32: 4, BF16: 2, F16: 2}
 HALF_ULP_REL = {BF16: 2.0 * U16[BF16], F16: U16[F16]}               # see the module docstring
 
-# ---- constants of the dispatch (tests/test_gemm_cases_cpu.py reads the same numbers out of the .hip / .h text) -----------------
+# ---- constants of the dispatch (tests/test_gemm_cases_cpu.py reads the same numbers out of mv_gemm_plan.h and the .hip text) ----
 GT_BM, GT_BN, GT_BK = 128, 128, 64           # the 128x128 kernel
 G2_BM, G2_BK = 256, 32                       # the ring kernels: 256 rows, stages of 32 x KS
 RING_320_ROWS = 320
@@ -82,7 +82,7 @@ def cdiv(a, b):
 
 
 def gemm_route(ta, tb, M, N, K, splitk, f16, rows256=False, force=0, nj=0, rounds=1, n_cu=DEFAULT_CUS):
-    """mv_gemm.hip: gemm_route.  -> dict(big, variant, tiles, sk_auto, rule)"""
+    """mv_gemm_plan.h: the route of mv_gemm_plan.  -> dict(big, variant, tiles, sk_auto, rule)"""
     tm2 = cdiv(M, 256)
     t256, t128 = tm2 * cdiv(N, 256), tm2 * cdiv(N, 128)
     wide_nt = (not ta) and (not tb) and N >= WIDE_NT_MIN_N
@@ -136,7 +136,7 @@ def workspace_bytes(cfg, n_cu=DEFAULT_CUS):
 
 
 def ring_kernel(ta, tb, f16, v):
-    """the launchers' variant tables (mv_gemm_common.h: mv_launch_ring, mv_gemm_ring_{nt,nn,tn,tnn,tn4}.hip)"""
+    """the kernel a routed variant runs (mv_gemm_plan.h: mv_plan_ring_kernel)"""
     if v == 4 and ta and tb:
         return "ring_tn4"
     if not ta and not tb:

@@ -201,30 +201,20 @@ def test_the_constants_in_the_source_are_the_constants_of_the_predicates():
         return int(m.group(group))
     assert (num(gemm, r"#define GT_BM (\d+)"), num(gemm, r"#define GT_BN (\d+)"), num(gemm, r"#define GT_BK (\d+)")) == (G.GT_BM, G.GT_BN, G.GT_BK)
     assert (num(common, r"#define G2_BM (\d+)"), num(common, r"#define G2_BK (\d+)")) == (G.G2_BM, G.G2_BK)
-    route = gemm[gemm.index("static GemmRoute gemm_route("):gemm.index('extern "C" size_t mv_gemm_workspace_bytes')]
-    m = re.search(r"M >= (\d+) && N >= (\d+) && \(\(K & 7\) == 0 \|\| \(ta && tb\)\) && \(wide_nt \|\| ta\) &&\s+\(t128 >= (\d+) \|\| \(K >= (\d+) && splitk != 1\)\)", route)
-    assert m and tuple(int(x) for x in m.groups()) == (G.BIG_MIN_M, G.BIG_MIN_N, G.BIG_MIN_T128, G.BIG_LONG_K)
-    assert num(route, r"wide_nt = !ta && !tb && N >= (\d+);") == G.WIDE_NT_MIN_N
-    m = re.search(r"splitk <= 1 && M >= (\d+) && N >= (\d+) && \(N & 7\) == 0 && \(K & 7\) == 0 && K >= (\d+)\)", route)
-    assert m and tuple(int(x) for x in m.groups()) == (G.ROUNDS_MIN_M, G.ROUNDS_MIN_N, G.ROUNDS_MIN_K)
-    m = re.search(r"c128 = \(\(s128 \+ 3 \* n_cu - 1\) / \(3 \* n_cu\)\) \* (\d+), c256 = \(\(t256 \+ n_cu - 1\) / n_cu\) \* (\d+),\s+c320 = rows256 \? \(1ll << 60\) : "
-                  r"\(\(t320 \+ n_cu - 1\) / n_cu\) \* (\d+);", route)
-    assert m and tuple(int(x) for x in m.groups()) == (G.ROUND_COST["128"], G.ROUND_COST["256"], G.ROUND_COST["320"])
-    assert "if (c256 < c128 && c256 <= c320)" in route and "if (c320 < c128 && c320 < c256)" in route
-    m = re.search(r"c256 = \(\(t256 \+ n_cu - 1\) / n_cu\) \* (\d+), c320 = \(\(t320 \+ n_cu - 1\) / n_cu\) \* (\d+);\s+if \(c320 < c256\)", route)
-    assert m and (int(m.group(1)), int(m.group(2))) == (G.WIDE_COST["256"], G.WIDE_COST["320"])
-    assert route.count("(M + 319) / 320") == 3 and G.RING_320_ROWS == 320
-    m = re.search(r"slots = v128 \? (\d+) : (\d+);", route)
-    assert m and (int(m.group(1)), int(m.group(2))) == (G.SLOTS_RING_V128, G.SLOTS_RING)
-    m = re.search(r"r\.tiles < slots && K >= (\d+)\) \{ long long sk = slots / r\.tiles; if \(sk > K / (\d+)\) sk = K / \2; if \(sk > (\d+)\) sk = \3;", route)
-    assert m and tuple(int(x) for x in m.groups()) == (G.SK_MIN_K, G.SK_DEPTH, G.SK_CAP_RING)
-    m = re.search(r"r\.tiles < (\d+) && K >= (\d+)\) \{ long long sk = (\d+) / r\.tiles; if \(sk > K / (\d+)\) sk = K / \4; if \(sk > (\d+)\) sk = \5;", route)
-    assert m and tuple(int(x) for x in m.groups()) == (G.SLOTS_128, G.SK_MIN_K, G.SLOTS_128_SK, G.SK_DEPTH, G.SK_CAP_128)
-    assert "r.variant = g_mv_gemm_nj ? g_mv_gemm_nj : (ta ? 24 : 14);" in route and "if (r.variant == 10 && ta) r.variant = 24;" in route
-    assert "if (r.variant == 2 && !(f16 && ta == tb)) r.variant = ta ? 24 : 14;" in route
-    # the slab arithmetic of the three kernel families
-    assert "kchunk = (kchunk + 63) / 64 * 64;" in gemm and "kchunk = (kchunk + GT_BK - 1) / GT_BK * GT_BK;" in gemm and "kchunk = (kchunk + 15) / 16 * 16;" in gemm
-    assert "const bool sb = g_mv_gemm_nj != 32;" in gemm and "dim3 grid((N + 63) / 64, (M + 63) / 64, splitk)" in gemm
+    # the thresholds of the dispatch are named constants of mv_gemm_plan.h; what the plan does with them is compared with plan() call by
+    # call in tests/test_gemm_plan_cpu.py
+    plan = _src("mv_gemm_plan.h")
+
+    def const(name):
+        return num(plan, r"\b%s = (\d+)[,;]" % name)
+    assert (const("T128"), const("T128_BK")) == (G.GT_BM, G.GT_BK) and G.GT_BN == G.GT_BM
+    assert "static_assert(GT_BM == T128 && GT_BN == T128 && GT_BK == T128_BK" in gemm
+    assert (const("RING_ROWS"), const("RING_320_ROWS"), const("RING_BK")) == (G.G2_BM, G.RING_320_ROWS, 2 * G.G2_BK)
+    assert (const("VALU_TILE"), const("VALU_BK")) == (G.VALU_TILE, G.VALU_BK)
+    for name in ("BIG_MIN_M", "BIG_MIN_N", "BIG_MIN_T128", "BIG_LONG_K", "WIDE_NT_MIN_N", "ROUNDS_MIN_M", "ROUNDS_MIN_N", "ROUNDS_MIN_K", "SLOTS_128", "SLOTS_128_SK",
+                 "SLOTS_RING", "SLOTS_RING_V128", "SK_MIN_K", "SK_DEPTH", "SK_CAP_128", "SK_CAP_RING"):
+        assert const(name) == getattr(G, name), name
+    assert {k: const("ROUND_COST_" + k) for k in G.ROUND_COST} == G.ROUND_COST and {k: const("WIDE_COST_" + k) for k in G.WIDE_COST} == G.WIDE_COST
     assert num(ring, r"constexpr int EPI_OPS = (\d+);") == G.EPI_OPS and ring.count("constexpr int EPI_OPS = %d;" % G.EPI_OPS) == 2
     # the 16-byte-store condition and the epilogue classes it names
     assert ("#define G2_WIDE_COND(NJ_) ((WIDE_E || (WIDE_R && p.r8_ok)) && (NJ_) == 4 && p.vec8_ok && p.c_dtype != MV_F32 && !p.accumulate && "
@@ -235,17 +225,7 @@ def test_the_constants_in_the_source_are_the_constants_of_the_predicates():
     assert "if (!CONV && G2_WIDE_COND(NJ))" in gemm and "fast[j] = p.vec_ok && (p.N - n >= 4);" in gemm
     assert "const bool lane_fast = ((E_) >= 0) && col_on && p.vec_ok && (p.N - ncol >= 4);" in common and "if (HAS_R && __all(lane_fast || !col_on))" in common
     assert "const bool full = (m0 + G2_BM <= p.M) && (n0 + BN <= p.N) && ((p.N & 3) == 0) && (p.splitk > 1 || p.vec_ok);" in ring
-    # the launchers' variant tables (ring_kernel)
-    nt, nn, tn, tnn, tn4 = (_src("mv_gemm_ring_%s.hip" % s) for s in ("nt", "nn", "tn", "tnn", "tn4"))
-    assert "if (variant == 4 && ta && tb) return mv_launch_ring_tn4(" in common
-    assert "if (variant == 2) LAUNCH_RING(false, false, 4, 2, 3, 1, true);" in nt and "if (variant == 2) LAUNCH_RING(true, true, 4, 2, 3, 1, true);" in tn
-    assert nt.count("variant == 2)") == 1 and tn.count("variant == 2)") == 1 and "variant == 2)" not in nn + tnn       # f16 operands only
-    assert "if (variant == 24) LAUNCH_PRING(false, false, 4, 4, 2, false);" in nt and nt.count("LAUNCH_PRING") == 1
-    assert nt.count("LAUNCH_RING_MI(false, false, 4, 4, 2, 2, ") == 2 and nn.count("LAUNCH_RING_MI(false, true, 4, 4, 2, 2, ") == 2
-    assert "if (variant == 24) LAUNCH_PRING(false, true, 4, 4, 2, false);" in nn and nn.count("LAUNCH_PRING") == 1
-    assert "else if (variant == 24) LAUNCH_PRING(true, true, 4, 4, 2, true);" in tn and "if (variant == 24) LAUNCH_PRING(true, true, 4, 4, 2, false);" in tn
-    assert "if (f16) return MV_E_DTYPE;" in tnn and "if (variant == 24) LAUNCH_PRING(true, false, 4, 4, 2, false);" in tnn
-    assert "LAUNCH_RING(true, true, 4, 4, 4, 1, true);" in tn4 and "LAUNCH_RING(true, true, 4, 4, 4, 1, false);" in tn4
+    # (the launchers' variant tables -- ring_kernel -- are mv_plan_ring_kernel of mv_gemm_plan.h now: tests/test_gemm_plan_cpu.py)
     for k, (bm, bn, bk) in G.RING_TILE.items():
         assert bm in (G.G2_BM, G.RING_320_ROWS) and bn in (256, 128) and bk in (G.G2_BK, 2 * G.G2_BK), k
     # all three bodies of the split-K reduce apply alpha

@@ -154,7 +154,7 @@ def test_the_constants_in_the_source_are_the_constants_of_the_restatement():
     assert num(grp, r"const int GM = (\d+), per_group = GM \* tiles_n;") == GG.GM
     assert "const int q = n >> 3, r = n & 7, xcd = u & 7, in = u >> 3;" in grp and GG.XCDS == 8
     assert "h.tail = h.split > 1 ? rem : 0;" in grp and "kc = (kc + MV_GROUP_BK - 1) / MV_GROUP_BK * MV_GROUP_BK;" in grp
-    kern = ring[ring.index("void gemm_pring_grouped_kernel("):ring.index("#define LAUNCH_PRING(")]
+    kern = ring[ring.index("void gemm_pring_grouped_kernel("):ring.index("// Launch of the ring kernel a plan names")]
     assert num(kern, r"constexpr int EPI_OPS = (\d+);") == GG.EPI_OPS
     # what unit_state() restates: the one-stage floor, vec_ok, full, and what either kind of unit leaves in epi_ops
     assert kern.count("max(1, (d.kend - d.kbeg + BKS - 1) / BKS)") == 2
@@ -165,7 +165,7 @@ def test_the_constants_in_the_source_are_the_constants_of_the_restatement():
     red = tn[tn.index("void splitk_reduce_grouped_kernel("):tn.index("int mv_launch_ring_tn_grouped(")]
     assert "const bool vec = ((ldc & 3) == 0) && ((((uintptr_t)C) & 15) == 0) && ((N & 3) == 0);" in red
     assert "const int nsl = (e->K + e->kchunk - 1) / e->kchunk;" in red and "if (m >= M || n >= N) continue;" in red
-    assert "const int n_blk = h.n_blocks < grouped_blocks() ? h.n_blocks : grouped_blocks();" in gemm
+    assert "const int n_max = mv_persistent_blocks(gemm_knobs().persistent_cus, gemm_n_cu());" in gemm and "const int n_blk = h.n_blocks < n_max ? h.n_blocks : n_max;" in gemm
     assert "const dim3 grid(units < n_blk ? units : n_blk), block(512);" in tn
 
 
