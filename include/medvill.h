@@ -302,6 +302,24 @@ int mv_attn_bwd(int dtype, const void* qkv, const void* ctx, const void* dctx, c
                 void* dqkv, float* delta, int B, int L, int A, int dh,
                 float p_drop, const uint32_t* dropbits, const int32_t* cu, int total_rows, const int32_t* qlim, void* stream);
 
+/* The attention probabilities of one layer, from what its forward left behind (qkv, lse, mask words, tile classes, keep-bits):
+ *   P[b,a,i,j] = exp(q_i.k_j / sqrt(dh) + (mask[b,i,j] ? 0 : -10000) - lse[b,a,i])
+ * -- HF BertSelfAttention's attention_probs (model.py:301-320 with output_attentions), the third value of the encoder protocol
+ * (models/cxrbert_origin.py:126-130).  Dense [B*L] row layout only (no packed rows, no query limit).
+ *   dtype      encoding of qkv (MV_F32, MV_BF16, MV_F16); out_dtype: MV_F32 or that same encoding (anything else: MV_E_ARG)
+ *   probs      [B, A, L, L] row-major, or [B, L, L] when head_mean != 0: the arithmetic mean over the A heads, summed in f32 by the
+ *              one thread block that owns the tile (no atomics, no second pass).  Nothing outside it is written.
+ *   p_drop > 0 the keep-bits `dropbits` of mv_attn_dropmask are applied and survivors scaled as in mv_attn_fwd: the result is the
+ *              matrix the context was computed from (what HF returns in train mode).
+ * Tiles of class 0 (skipped by the forward) are written as zeros: every one of their entries is exp(-10000 + ...) = 0 in fp32.
+ * 16-bit path: dh must be 64 (v_mfma_f32_32x32x16_{f16,bf16}; 16-byte stores when L is a multiple of 4 (f32 output) / 8 (16-bit
+ * output), element stores otherwise); f32 path and the debug library's impl knob: dh <= 128.  ceil(L/64) <= 64.
+ * MV_E_ARG: a null pointer, a size that is not positive, a bad out_dtype, p_drop > 0 without dropbits.  MV_E_SHAPE: the limits above,
+ * qkv or probs not 16-byte aligned, dropbits not 64-byte aligned, a qkv of 2^31 bytes or more on the 16-bit path (it is read through a
+ * buffer descriptor; probs is addressed with 64-bit offsets and has no such limit).  A refused call launches nothing. */
+int mv_attn_probs(int dtype, const void* qkv, const uint32_t* bits, const uint8_t* tileinfo, const float* lse, void* probs,
+                  int out_dtype, int B, int L, int A, int dh, float p_drop, const uint32_t* dropbits, int head_mean, void* stream);
+
 /* ---- LayerNorm ------------------------------------------------------------------------------
  * y = (x-mean)/sqrt(var+eps)*gamma+beta over the last dim (HF LayerNorm eps=1e-12 in the
  * encoder; TF-style BertLayerNorm eps=1e-5 of cxrbert_origin.py:189-202 in the MLM head).

@@ -419,6 +419,9 @@ class CXRBERT(nn.Module):
         # one rank is initialised: DistributedDataParallel's reducer; a Tensor.register_hook on a Parameter), True / False force it
         self.lazy_logits, self.recognise_masks, self.grad_views = False, True, None
         self.grad_in_loss = True          # lazy logits: the loss runs the head once, with its gradient (see _LazyLossFn)
+        # attention output (cxrbert_origin.py:126-130, output_attentions=True): False, True (every layer) or an iterable of layer indices;
+        # enc(...)[2] is then a tuple of detached [B, A, L, L] tensors ([B, L, L] with attention_head_mean), ascending by layer
+        self.output_attentions, self.attention_head_mean, self.attention_dtype = False, False, torch.float32
         self.n_masks_seen = self.n_masks_recognised = 0
         self._lazy_rows = None
         self._opt_versions = None
@@ -563,9 +566,51 @@ class CXRBERT(nn.Module):
         self._want_grad = torch.is_grad_enabled()        # (grad mode is always off inside autograd.Function.forward)
         return _CXRBertFn.apply(self, want_heads, cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, *params)
 
+    def _attention_layers(self, layers):
+        """True / iterable of layer indices -> the set the engine is asked for"""
+        n = self.cfg.layers
+        if layers is True:
+            return set(range(n))
+        want = {int(l) for l in layers}
+        if not want or min(want) < 0 or max(want) >= n:
+            raise ValueError(f"attention layers must be indices in 0..{n - 1}, got {sorted(want)}")
+        return want
+
     def _enc_forward(self, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok):
-        hidden, pooled = self._run(False, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok)
-        return hidden, pooled, None
+        eng = self.engine
+        if self.output_attentions is False or self.output_attentions is None:
+            hidden, pooled = self._run(False, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok)
+            return hidden, pooled, None
+        if eng.device.type != "cuda":
+            raise RuntimeError("medvill HIP kernels need CUDA(ROCm) tensors; there is no CPU fallback")
+        prev = eng.attn_out
+        eng.attn_out = dict(layers=self._attention_layers(self.output_attentions), head_mean=bool(self.attention_head_mean),
+                            dtype=self.attention_dtype)
+        try:
+            hidden, pooled = self._run(False, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok)
+            # detached (a stated deviation from the reference: nobody back-propagates through the returned probabilities)
+            return hidden, pooled, tuple(eng.S["attn_probs"])
+        finally:
+            eng.attn_out = prev
+
+    @torch.no_grad()
+    def attention_maps(self, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, layers=None, head_mean=False, dtype=torch.float32):
+        """The attention probabilities of the encoder on one batch: a tuple with one [B, A, L, L] tensor per requested layer
+        ([B, L, L], the mean over the heads, with head_mean), ascending by layer; layers None = every layer.  dtype: torch.float32 or the
+        engine's forward encoding.  Runs the encoder only, without gradients, in the model's current train / eval mode (in train mode
+        the dropout keep-bits are applied: the matrices the contexts were computed from).  The engine's train / keep-activations /
+        dropout-counter / attention-output state is restored afterwards, so a later training step draws the masks it would have drawn."""
+        eng = self.engine
+        if eng.device.type != "cuda":
+            raise RuntimeError("medvill HIP kernels need CUDA(ROCm) tensors; there is no CPU fallback")
+        want = self._attention_layers(True if layers is None else layers)
+        prev = (eng.training, eng.keep_acts, eng.drop_counter, eng.attn_out)
+        eng.attn_out = dict(layers=want, head_mean=bool(head_mean), dtype=dtype)
+        try:
+            self._run(False, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok)
+            return tuple(eng.S["attn_probs"])
+        finally:
+            eng.training, eng.keep_acts, eng.drop_counter, eng.attn_out = prev
 
     def forward(self, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, txt_labels=None):
         """cxrbert_origin.py:144-149.  txt_labels (optional, lazy logits only; not part of the reference's signature): the MLM labels the loss

@@ -217,6 +217,10 @@ class Engine:
         self._side = None             # side HIP stream for the weight-gradient GEMMs of the backward
         self.training = False         # dropout is active only when True (CXRBERT.train() / TrainStep(train=True))
         self.keep_acts = True         # False: the forward keeps no per-layer activations (inference; see encoder_forward)
+        # attention output (CXRBERT.output_attentions / attention_maps): None, or dict(layers=set of layer indices, head_mean=bool,
+        # dtype=torch.float32 or the forward encoding) -- the requested layers' probabilities are written by mv_attn_probs right behind
+        # their attention forward into tensors of their own, S["attn_probs"].  Padded rows only; TrainStep never sets it
+        self.attn_out = None
         # dropout stream: keyed by torch's seed (set_seed of utils/utils.py:9-16 -> torch.manual_seed), a per-rank offset
         # added by TrainStep under data parallelism, and a counter advanced once per forward (every step draws fresh masks)
         # f16 forward path: the encoder layers' LayerNorm inputs (residual sums, written by the output-projection / FFN-down GEMMs
@@ -485,6 +489,9 @@ class Engine:
             self.sync_shadow()
         S = self.S = dict(B=B, T=T, N=N, L=Lq, M=B * Lq, cu=None, rowmap=None, inv=None, sel=None, n_lab=0, tq=None, tail_sel=None, layers=[],
                           p_drop=float(cfg.dropout) if self.training else 0.0, keep=bool(self.keep_acts))
+        S["attn_probs"] = []
+        if self.attn_out is not None and (pack or tail_rows is not None):
+            raise ValueError("attention output runs on the padded row layout: no packed rows, no consumed-rows last layer")
         self._row_plan(attn_mask, pack, tail_rows)
         self.drop_counter += 1
         S["drop_keys"] = self._drop_keys(cfg.layers)
@@ -639,6 +646,16 @@ class Engine:
             torch.cuda.current_stream().wait_event(ev)
         ops.attn_fwd(qkv, S["bits"], S["tinfo"], ctx, lse, B, Lq, A, H // A, p_drop=pd, cu=cu,
                      total_rows=M, ctx_bf16=ctx_b if dual else None, dropbits=a_["dropbits"], qlim=tq.qlim if tq is not None else None)
+        ao = self.attn_out
+        if ao is not None and l in ao["layers"]:
+            # the layer's probabilities, from the qkv / lse / keep-bits that are live right here (also with one scratch set, keep False).
+            # A tensor of its own, not a _buf: it is handed to the caller
+            hm, odt = bool(ao.get("head_mean", False)), ao.get("dtype", f32)
+            if odt not in (f32, qkv.dtype):
+                raise ValueError(f"attention output dtype must be torch.float32 or the forward encoding {qkv.dtype}, not {odt}")
+            probs = torch.empty((B, Lq, Lq) if hm else (B, A, Lq, Lq), dtype=odt, device=self.device)
+            ops.attn_probs(qkv, S["bits"], S["tinfo"], lse, probs, B, Lq, A, H // A, p_drop=pd, dropbits=a_["dropbits"], head_mean=hm)
+            S["attn_probs"].append(probs)
         if last and S["sel"] is not None:
             # last layer: only the labelled rows and the first row of every sample are consumed downstream.  From here on M is the
             # number of those rows

@@ -191,6 +191,21 @@ def attn_fwd(qkv, bits, tileinfo, ctx, lse, B, Lq, A, dh, p_drop=0.0, cu=None, t
     L.check(rc, "mv_attn_fwd")
 
 
+def attn_probs(qkv, bits, tileinfo, lse, out, B, Lq, A, dh, p_drop=0.0, dropbits=None, head_mean=False):
+    """The layer's attention probabilities (see mv_attn_probs) into `out`: [B, A, L, L], or [B, L, L] with head_mean; f32 or qkv's
+    encoding.  Dense rows only; p_drop > 0 applies the layer's keep-bits `dropbits`."""
+    L.require_cuda(qkv, bits, tileinfo, lse, out, dropbits)
+    n = B * (1 if head_mean else A) * Lq * Lq
+    if out.dtype not in (torch.float32, qkv.dtype) or out.numel() != n or not out.is_contiguous():
+        raise TypeError("attn_probs: out must be a contiguous f32 (or qkv-encoded) tensor of B*A*L*L elements (B*L*L with head_mean)")
+    if lse.dtype != torch.float32 or lse.numel() < B * A * Lq:
+        raise TypeError("attn_probs: lse must be f32 [B, A, L]")
+    rc = _lib().mv_attn_probs(L.dt_of(qkv), L.ptr(qkv), L.ptr(bits), L.ptr(tileinfo), L.ptr(lse), L.ptr(out), L.dt_of(out), B, Lq, A, dh,
+                              float(p_drop), L.ptr(dropbits), int(bool(head_mean)), L.stream_ptr())
+    L.check(rc, "mv_attn_probs")
+    return out
+
+
 def attn_bwd(qkv, ctx, dctx, lse, bits, tileinfo, dqkv, delta, B, Lq, A, dh, p_drop=0.0, cu=None, total_rows=0, dropbits=None, qlim=None):
     L.require_cuda(dropbits, qlim)
     rc = _lib().mv_attn_bwd(L.dt_of(qkv), L.ptr(qkv), L.ptr(ctx), L.ptr(dctx), L.ptr(lse), L.ptr(bits), L.ptr(tileinfo),
