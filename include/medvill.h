@@ -517,7 +517,26 @@ int mv_scaler_update(float* state, int growth_interval, float growth, float back
  *   largest logp (k <= 16) in descending order, ties to the lower column.  lse (nullable) f32 [R].  No [R,V] output.
  *   A -inf logit adds nothing to lse and ranks last (logp -inf, by column); a row that is -inf throughout is outside the contract.
  * mv_embed_rows: out[r] = LN(E[ids[r]] + Ty[seg[r]] + P[pos[r]]) (HF BertEmbeddings of one token), tables in dtype, gamma /
- *   beta f32; indices int64, clamped into their tables.  The tables are dense: row i of E / P / Ty starts at element i * H.  */
+ *   beta f32; indices int64, clamped into their tables.  The tables are dense: row i of E / P / Ty starts at element i * H.
+ *
+ * n-gram blocking (the reference decoder's forbid_duplicate_ngrams / ngram_size / forbid_ignore_set, model.py:1373-1426, kept on
+ * the device).  Two additive entry points:
+ * mv_ngram_ban: one beam step for R beams whose histories hold `len` words each.
+ *     hist_out[r, :len] = hist_in[parent[r], :len],  hist_out[r, len] = (int32)y[r]
+ *   hist_in / hist_out int32 [R, ld_h]; parent int64 [R] (what torch index arithmetic on the back pointers gives; nullable:
+ *   identity; a value outside [0, R) reads row 0 / R-1); y int64 [R].  hist_out must not overlap hist_in (MV_E_ARG): the gather
+ *   reads rows other blocks write.  With seq = hist_out[r, :len+1] and tail = its last n-1 words, the banned words of beam r are
+ *     none when len + 1 < n, none when a word of tail is in ignore, else every seq[i+n-1] with seq[i:i+n-1] == tail
+ *     (0 <= i <= len+1-n; the last windows overlap the tail, so a run of one word bans that word) that is not in ignore;
+ *   ban int32 [R, ld_ban] receives them once each in ascending order, nban int32 [R] their number.  Columns of ban at and
+ *   beyond nban[r] and columns of hist_out beyond len are not written.  ignore int32 [n_ign], nullable when n_ign = 0.
+ *   Limits: 2 <= n <= 8 (MV_E_ARG); len + 1 <= ld_h, len + 1 <= 1024, n_ign <= 256, ld_ban >= len + 2 - n (MV_E_SHAPE).
+ * mv_logprob_topk_banned: mv_logprob_topk on  logp[c] = fl(x[c] - lse),  logp[c] = fl(logp[c] - 10000) for every c listed in
+ *   ban[r, :nban[r]] (int32 [R, ld_ban] / int32 [R]; ids outside [0, V) are ignored, an id listed twice counts once), then
+ *   logp[eos_penalty_id] = -10000 exactly (also when that column is banned).  Banned columns stay in lse.  A banned column
+ *   ranks by its penalised value, ties to the lower column.  ban == NULL, or nban[r] == 0, gives the bits mv_logprob_topk
+ *   gives (vals, idx, lse).  V <= 131072 (one LDS bit per column; MV_E_SHAPE), k <= 16, k <= V.  nban[r] is clamped to
+ *   [0, ld_ban].  Rows whose unbanned log-probs themselves reach -10000 are outside the contract.  */
 int mv_gemm_rows(int dtype, int M, int N, int K, const void* x, int ldx, const void* W, int ldw, void* C, int ldc, int c_dtype,
                  const float* bias, int epi, const void* R, int ldr, int r_dtype, void* stream);
 int mv_attn_decode(int dtype, const void* q, int ldq, const void* k_cache, const void* v_cache, int ldkv, const int32_t* slots,
@@ -528,6 +547,10 @@ int mv_logprob_topk(const float* logits, int ld, int R, int V, int k, int eos_pe
 int mv_embed_rows(int dtype, const int64_t* ids, const int64_t* pos, const int64_t* seg, const void* E, const void* P, const void* Ty,
                   const float* gamma, const float* beta, void* out, int ldo, int R, int H, int V, int maxpos, int ntype, float eps,
                   void* stream);
+int mv_ngram_ban(const int32_t* hist_in, int32_t* hist_out, int ld_h, const int64_t* parent, const int64_t* y, int R, int len, int n,
+                 const int32_t* ignore, int n_ign, int32_t* ban, int ld_ban, int32_t* nban, void* stream);
+int mv_logprob_topk_banned(const float* logits, int ld, int R, int V, int k, int eos_penalty_id, const int32_t* ban, int ld_ban,
+                           const int32_t* nban, float* vals, int64_t* idx, float* lse, void* stream);
 
 /* ---- VQA fine-tuning and answer prediction (csrc/mv_vqa.hip) --------------------------------------
  * The answer classifier of the reference's VQA model (Downstream_task/report_generation_and_vqa/sc/pytorch_pretrained_bert/

@@ -86,6 +86,8 @@ PROTOTYPES = {
     "mv_attn_decode": [i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, sz, vp],
     "mv_logprob_topk": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "mv_embed_rows": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp],
+    "mv_ngram_ban": [vp, vp, i32, vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp],
+    "mv_logprob_topk_banned": [vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp],
     # VQA (csrc/mv_vqa.hip)
     "mv_bce_fwd_bwd": [vp, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, f32, vp, vp, vp, vp],
     "mv_rows_mul": [i32, vp, i32, vp, vp, i32, vp, i32, i32, vp, i32, vp],

@@ -8,7 +8,9 @@ Follows the reference's BertForSeq2SeqDecoder.beam_search
   final pick   per sample, over the frames up to the first frame whose K words are all EOS: a candidate counts when its word is EOS or
                it lies in that last frame; maximise score + length_penalty * (frame + 1), then follow the back pointers.
 The min_len rule (EOS log-prob := -10000 for the first min_len steps) is applied where the log-probs are made (mv_logprob_topk).
-n-gram blocking (forbid_duplicate_ngrams / forbid_ignore_set) depends on tokenizer words and is not supported.
+n-gram blocking (the reference's forbid_duplicate_ngrams / ngram_size / forbid_ignore_set) is applied there too: the histories and
+the ban lists live on the device (mv_ngram_ban after every step, mv_logprob_topk_banned at the next; generate()'s
+no_repeat_ngram_size / no_repeat_ignore_ids); this class only hands over its parents and word ids.
 
 The KV cache is shared, not copied: every beam owns one row of an int32 slot table (the cache rows it attends to), and re-ordering
 the beams re-orders those rows (`reorder_slot_table`).

@@ -6,6 +6,9 @@
 //   mv_attn_decode   ctx[r, head] = softmax(q k^T / sqrt(dh)) v over the cache slots listed for query row r; split-KV + lse merge
 //   mv_logprob_topk  row log-softmax (f32) and its top-k (k <= 16, ties to the lower index), optional EOS column := -10000
 //   mv_embed_rows    x[r] = LN(E[id] + Ty[seg] + P[pos])  (HF BertEmbeddings for one token row)
+//   mv_ngram_ban     one beam step of n-gram blocking: gather the parents' word histories, append the chosen word, list the words
+//                    that would repeat an n-gram
+//   mv_logprob_topk_banned   mv_logprob_topk with -10000 added to the log-prob of every listed word of the row
 #include "mv_common.h"
 #include "mv_gemm_common.h"
 
@@ -421,6 +424,230 @@ extern "C" int mv_embed_rows(int dtype, const int64_t* ids, const int64_t* pos, 
     hipLaunchKernelGGL(embed_rows_kernel<f16_t>, dim3(R), dim3(256), lds, stream, ids, pos, seg, (const f16_t*)E, (const f16_t*)P,
                        (const f16_t*)Ty, gamma, beta, (f16_t*)out, ldo, H, V, maxpos, ntype, eps);
   else return MV_E_DTYPE;
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mv_ngram_ban
+// Block = one beam.  The beam's new history (its parent's words, then the word just chosen) is staged in LDS and written out; every
+// window of n - 1 words is compared with the last n - 1 (the tail), the word behind a matching window is a candidate.  Candidates
+// are few: the duplicates are dropped and the rest ranked by counting, so the list comes out ascending without a sort network.
+#define NB_MAX_LEN 1024      // words of one history, the new one included
+#define NB_MAX_IGN 256       // ignore ids
+#define NB_MIN_N 2
+#define NB_MAX_N 8
+
+__global__ __launch_bounds__(256) void ngram_ban_kernel(const int32_t* __restrict__ hist_in, int32_t* __restrict__ hist_out, int ld_h,
+                                                       const int64_t* __restrict__ parent, const int64_t* __restrict__ y, int R, int len,
+                                                       int n, const int32_t* __restrict__ ignore, int n_ign, int32_t* __restrict__ ban,
+                                                       int ld_ban, int32_t* __restrict__ nban) {
+  __shared__ int32_t seq[NB_MAX_LEN];
+  __shared__ int32_t cand[NB_MAX_LEN];
+  __shared__ int32_t keep[NB_MAX_LEN];
+  __shared__ int32_t ign[NB_MAX_IGN];
+  __shared__ int count;
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int L = len + 1;                               // words of the new history
+  long long p = parent ? (long long)parent[r] : r;
+  p = min(max(p, 0ll), (long long)R - 1);              // a parent outside [0, R) reads the first / last row
+  const int32_t* src = hist_in + (size_t)p * ld_h;
+  int32_t* dst = hist_out + (size_t)r * ld_h;
+  for (int i = tid; i < L; i += 256) {
+    const int32_t w = i < len ? src[i] : (int32_t)y[r];
+    seq[i] = w;
+    dst[i] = w;
+  }
+  for (int i = tid; i < n_ign; i += 256) ign[i] = ignore[i];
+  if (tid == 0) count = 0;
+  __syncthreads();
+  const int W = L - n + 1;                             // windows of n - 1 words that have a word behind them
+  if (W <= 0) {                                        // fewer than n words: nothing is banned
+    if (tid == 0) nban[r] = 0;
+    return;
+  }
+  const int32_t* tail = seq + L - (n - 1);
+  int hit = 0;                                         // an ignore word in the tail switches the rule off for this beam
+  if (tid < n - 1)
+    for (int j = 0; j < n_ign; ++j) hit |= (ign[j] == tail[tid]);
+  if (__syncthreads_or(hit)) {
+    if (tid == 0) nban[r] = 0;
+    return;
+  }
+  for (int i = tid; i < W; i += 256) {
+    bool ok = true;
+    for (int j = 0; j < n - 1; ++j) ok &= (seq[i + j] == tail[j]);
+    const int32_t w = seq[i + n - 1];
+    if (ok)
+      for (int j = 0; j < n_ign; ++j) ok &= (ign[j] != w);
+    cand[i] = ok ? 1 : 0;
+  }
+  __syncthreads();
+  for (int i = tid; i < W; i += 256) {                 // a word several windows ban counts at its first window
+    int first = cand[i];
+    if (first) {
+      const int32_t w = seq[i + n - 1];
+      for (int j = 0; j < i; ++j) first &= !(cand[j] && seq[j + n - 1] == w);
+    }
+    keep[i] = first;
+  }
+  __syncthreads();
+  for (int i = tid; i < W; i += 256) {
+    if (!keep[i]) continue;
+    const int32_t w = seq[i + n - 1];
+    int rank = 0;
+    for (int j = 0; j < W; ++j) rank += (keep[j] && seq[j + n - 1] < w);
+    if (rank < ld_ban) ban[(size_t)r * ld_ban + rank] = w;        // rank < W <= ld_ban (checked by the host)
+    atomicAdd(&count, 1);
+  }
+  __syncthreads();
+  if (tid == 0) nban[r] = count;
+}
+
+extern "C" int mv_ngram_ban(const int32_t* hist_in, int32_t* hist_out, int ld_h, const int64_t* parent, const int64_t* y, int R, int len,
+                            int n, const int32_t* ignore, int n_ign, int32_t* ban, int ld_ban, int32_t* nban, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!hist_in || !hist_out || !y || !ban || !nban || R <= 0 || len < 0 || ld_h <= 0 || ld_ban < 0 || n_ign < 0) return MV_E_ARG;
+  if (n < NB_MIN_N || n > NB_MAX_N) return MV_E_ARG;
+  if (n_ign > 0 && !ignore) return MV_E_ARG;
+  if (len + 1 > NB_MAX_LEN || n_ign > NB_MAX_IGN) return MV_E_SHAPE;
+  if (ld_h < len + 1 || ld_ban < len + 2 - n) return MV_E_SHAPE;
+  {                                                    // the gather reads rows the same launch writes: the two histories must not overlap
+    const uintptr_t a = (uintptr_t)hist_in, b = (uintptr_t)hist_out;
+    const uintptr_t span = ((size_t)(R - 1) * ld_h + len + 1) * sizeof(int32_t);
+    if (a < b + span && b < a + span) return MV_E_ARG;
+  }
+  hipLaunchKernelGGL(ngram_ban_kernel, dim3(R), dim3(256), 0, stream, hist_in, hist_out, ld_h, parent, y, R, len, n, ignore, n_ign, ban,
+                     ld_ban, nban);
+  MV_CHECK_LAUNCH();
+  return MV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mv_logprob_topk_banned
+// mv_logprob_topk's block with the row's banned words marked in an LDS bitmap over the vocabulary.  The scan keeps banned columns
+// out of the per-thread lists (as it keeps the penalised EOS column out); once the log-sum-exp is known they enter with their final
+// value fl(fl(x - lse) - 10000).  List entries of banned columns carry ~column (negative) and their value is a log-prob; all other
+// entries are raw logits as in mv_logprob_topk.  Two unbanned entries compare as there, so a row without bans selects bit for bit
+// what mv_logprob_topk selects; a comparison that involves a banned entry is made on the final values (ties to the lower column).
+#define TKB_MAX_V 131072     // bitmap: one bit per column, 16 KiB of LDS
+
+__device__ __forceinline__ bool tkb_better(float va, int ia, float vb, int ib, float lse, int eos) {
+  if ((ia | ib) >= 0) return tk_better(va, ia, vb, ib);
+  const float fa = ia < 0 ? va : (ia == eos ? -10000.0f : va - lse), fb = ib < 0 ? vb : (ib == eos ? -10000.0f : vb - lse);
+  const int ca = ia < 0 ? ~ia : ia, cb = ib < 0 ? ~ib : ib;
+  return fa > fb || (fa == fb && ca < cb);
+}
+
+template <int KM>
+__device__ __forceinline__ void tkb_insert(float (&v)[KM], int (&ix)[KM], float x, int c, float lse, int eos) {
+#pragma unroll
+  for (int i = 0; i < KM; ++i) {
+    if (tkb_better(x, c, v[i], ix[i], lse, eos)) {
+      const float tv = v[i];
+      const int ti = ix[i];
+      v[i] = x;
+      ix[i] = c;
+      x = tv;
+      c = ti;
+    }
+  }
+}
+
+template <int KM>
+__global__ __launch_bounds__(256) void logprob_topk_banned_kernel(const float* __restrict__ logits, int ld, int V, int k, int eos,
+                                                                 const int32_t* __restrict__ ban, int ld_ban, const int32_t* __restrict__ nban,
+                                                                 float* __restrict__ vals, int64_t* __restrict__ idx, float* __restrict__ lse_out) {
+  extern __shared__ unsigned bits[];                 // [(V + 31) / 32]
+  __shared__ float shm[4], shs[4], shv[4];
+  __shared__ int shi[4];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const float* x = logits + (size_t)row * ld;
+  const int nb = ban ? min(max(nban[row], 0), ld_ban) : 0;
+  const int nwords = (V + 31) >> 5;
+  if (nb > 0) {                                      // (block-uniform)
+    for (int w = tid; w < nwords; w += 256) bits[w] = 0u;
+    __syncthreads();
+    for (int j = tid; j < nb; j += 256) {
+      const int c = ban[(size_t)row * ld_ban + j];
+      if (c >= 0 && c < V) atomicOr(&bits[c >> 5], 1u << (c & 31));          // ids outside the vocabulary are ignored
+    }
+    __syncthreads();
+  }
+  float v[KM];
+  int ix[KM];
+#pragma unroll
+  for (int i = 0; i < KM; ++i) { v[i] = -INFINITY; ix[i] = 0x7fffffff; }
+  float m = -INFINITY, s = 0.f;
+  for (int c = tid; c < V; c += 256) {
+    const float xv = x[c];
+    if (xv > m) { s = s * __expf(m - xv) + 1.f; m = xv; }
+    else if (xv > -INFINITY) s += __expf(xv - m);
+    const bool banned = nb > 0 && ((bits[c >> 5] >> (c & 31)) & 1u);
+    if (c != eos && !banned) tk_insert<KM>(v, ix, xv, c);
+  }
+  float bm = wave_max(m);
+  if (lane == 0) shm[wid] = bm;
+  __syncthreads();
+  bm = fmaxf(fmaxf(shm[0], shm[1]), fmaxf(shm[2], shm[3]));
+  float bs = wave_sum(m > -INFINITY ? s * __expf(m - bm) : 0.f);
+  if (lane == 0) shs[wid] = bs;
+  __syncthreads();
+  const float lse = bm + __logf(shs[0] + shs[1] + shs[2] + shs[3]);
+  if (eos >= 0 && eos < V && tid == (eos & 255)) tk_insert<KM>(v, ix, -10000.0f + lse, eos);
+  if (nb > 0) {
+    for (int w = tid; w < nwords; w += 256) {        // every marked column once, whatever the list held twice
+      unsigned b = bits[w];
+      while (b) {
+        const int c = (w << 5) + __ffs((int)b) - 1;
+        b &= b - 1;
+        if (c == eos) continue;                      // banned and penalised: -10000 exactly, entered above
+        const float lp = x[c] - lse;
+        tkb_insert<KM>(v, ix, lp + -10000.0f, ~c, lse, eos);
+      }
+    }
+  }
+  for (int o = 0; o < k; ++o) {
+    float bv = v[0];
+    int bi = ix[0];
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_xor(bv, off);
+      const int oi = __shfl_xor(bi, off);
+      if (tkb_better(ov, oi, bv, bi, lse, eos)) { bv = ov; bi = oi; }
+    }
+    __syncthreads();
+    if (lane == 0) { shv[wid] = bv; shi[wid] = bi; }
+    __syncthreads();
+    bv = shv[0];
+    bi = shi[0];
+    for (int w = 1; w < 4; ++w)
+      if (tkb_better(shv[w], shi[w], bv, bi, lse, eos)) { bv = shv[w]; bi = shi[w]; }
+    if (ix[0] == bi) {                              // the owner pops its head
+#pragma unroll
+      for (int i = 0; i + 1 < KM; ++i) { v[i] = v[i + 1]; ix[i] = ix[i + 1]; }
+      v[KM - 1] = -INFINITY;
+      ix[KM - 1] = 0x7fffffff;
+    }
+    if (tid == 0) {
+      vals[(size_t)row * k + o] = bi < 0 ? bv : ((bi == eos) ? -10000.0f : bv - lse);
+      idx[(size_t)row * k + o] = bi < 0 ? ~bi : bi;
+    }
+  }
+  if (lse_out && tid == 0) lse_out[row] = lse;
+}
+
+extern "C" int mv_logprob_topk_banned(const float* logits, int ld, int R, int V, int k, int eos_penalty_id, const int32_t* ban, int ld_ban,
+                                      const int32_t* nban, float* vals, int64_t* idx, float* lse, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!logits || !vals || !idx || R <= 0 || V <= 0 || ld < V || k <= 0) return MV_E_ARG;
+  if (ban && (!nban || ld_ban <= 0)) return MV_E_ARG;
+  if (k > 16 || k > V || V > TKB_MAX_V) return MV_E_SHAPE;
+  const int eos = (eos_penalty_id >= 0 && eos_penalty_id < V) ? eos_penalty_id : -1;
+  const size_t lds = ban ? (size_t)((V + 31) / 32) * sizeof(unsigned) : 0;
+#define TKB_LAUNCH(KM_) \
+  hipLaunchKernelGGL(logprob_topk_banned_kernel<KM_>, dim3(R), dim3(256), lds, stream, logits, ld, V, k, eos, ban, ld_ban, nban, vals, idx, lse)
+  if (k == 1) TKB_LAUNCH(1);
+  else if (k <= 4) TKB_LAUNCH(4);
+  else TKB_LAUNCH(16);
+#undef TKB_LAUNCH
   MV_CHECK_LAUNCH();
   return MV_OK;
 }

@@ -636,7 +636,8 @@ class CXRBERT(nn.Module):
         return self._run(2, cls_tok, input_txt, attn_mask, segment, input_img, sep_tok)
 
     def generate(self, cls_tok, input_img, sep_tok, max_len=254, beam_size=1, min_len=0, length_penalty=0.0, eos_id=102, mask_id=103,
-                 forced_ids=None, return_traces=False, forbid_duplicate_ngrams=False, forbid_ignore_set=None):
+                 forced_ids=None, return_traces=False, forbid_duplicate_ngrams=False, forbid_ignore_set=None, no_repeat_ngram_size=0,
+                 no_repeat_ignore_ids=None):
         """Report generation with a KV cache (DESIGN.md "Generation"): iterated forward under the seq2seq mask, in eval mode, without
         gradients; the engine's train / keep-activations state is restored afterwards.
           cls_tok, sep_tok [B,1]; input_img as forward() takes it (region features + positions, or an image for img_encoder).
@@ -646,11 +647,18 @@ class CXRBERT(nn.Module):
           [B,T], step logits f32 [B, T, V]); step t's logits equal forward()'s MLM logits at text row t.
         beam_size K > 1: the reference's beam search (model.py:1239-1467; min_len, additive length_penalty) -> (ids [B, max_len],
           scores f32 [B]) and, with return_traces, the reference's traces {'pred_seq', 'scores', 'wids', 'ptrs'}.
-        forbid_duplicate_ngrams / forbid_ignore_set need tokenizer words: NotImplementedError."""
+        no_repeat_ngram_size n (0 = off, else 2..8), no_repeat_ignore_ids S (token ids, at most 256): the reference's n-gram blocking
+          (model.py:1373-1426), on the device.  Its `forbid_duplicate_ngrams=True, ngram_size=n, forbid_ignore_set=S` is
+          `no_repeat_ngram_size=n, no_repeat_ignore_ids=S` here; the reference's own keyword names raise NotImplementedError.  A word
+          that would complete an n-gram the beam already holds gets -10000 added to its log-prob, unless the beam's last n-1 words
+          or the word itself are in S.  With blocking on, beam_size=1 runs the beam search at K = 1 and returns what a beam call
+          returns (ids, scores [B]): the rule lives in the reference's beam_search, its separate greedy loop ignores the flags.
+          ValueError: n = 1 or n > 8, forced_ids together with blocking, more than 256 ignore ids, max_len > 1024."""
         from .generate import generate
         return generate(self, cls_tok, input_img, sep_tok, max_len=max_len, beam_size=beam_size, min_len=min_len,
                         length_penalty=length_penalty, eos_id=eos_id, mask_id=mask_id, forced_ids=forced_ids, return_traces=return_traces,
-                        forbid_duplicate_ngrams=forbid_duplicate_ngrams, forbid_ignore_set=forbid_ignore_set)
+                        forbid_duplicate_ngrams=forbid_duplicate_ngrams, forbid_ignore_set=forbid_ignore_set,
+                        no_repeat_ngram_size=no_repeat_ngram_size, no_repeat_ignore_ids=no_repeat_ignore_ids)
 
     # ------------------------------------------------------------------ state dict (reference key names)
     def state_dict(self, *a, **k):

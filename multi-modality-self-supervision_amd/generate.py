@@ -21,6 +21,9 @@ from ._lib import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, MV_F32
 from .beam import BeamSearch, reorder_slot_table
 
 PAD_ID = 0
+NGRAM_MIN, NGRAM_MAX = 2, 8          # mv_ngram_ban's range of n
+NGRAM_MAX_IGNORE = 256               # ... of ignore ids
+NGRAM_MAX_LEN = 1024                 # ... of words per history
 
 
 class Generator:
@@ -30,6 +33,7 @@ class Generator:
         self.eng = engine
         self.key = None
         self.bufs = {}
+        self.ngram = 0                               # n-gram blocking: off until ngram_on(); _alloc switches it off again
 
     # ------------------------------------------------------------------ buffers
     def _buf(self, name, shape, dtype):
@@ -60,6 +64,23 @@ class Generator:
         self.slot_row2 = torch.cat([r, r])
         self.mslot = self.mask_base + r
         self.ws = self._buf("ws", (16 * 2 * BK * cfg.heads * (H // cfg.heads + 2),), torch.float32)
+        self.ngram = 0
+
+    def ngram_on(self, n, ignore_ids):
+        """n-gram blocking for this call: two word histories per beam, used in alternation, and the ban list the next
+        step's top-k reads.  The upload of the ignore ids is the only host-to-device copy blocking adds."""
+        BK, max_len = self.BK, self.max_len
+        self.ngram = int(n)
+        self.hist = [self._buf(f"hist{i}", (BK, max_len), torch.int32) for i in range(2)]
+        self.ban = self._buf("ban", (BK, max_len), torch.int32)
+        self.nban = self._buf("nban", (BK,), torch.int32)
+        self.nban.zero_()                            # no ban exists before n words have been produced
+        self.ignore = torch.tensor(ignore_ids, dtype=torch.int32).to(self.eng.device) if ignore_ids else None
+
+    def ngram_update(self, t, parents, y):
+        """After step t's beams are chosen: every beam's history becomes its parent's plus its word, and its ban list is rebuilt."""
+        ops.ngram_ban(self.hist[t & 1], self.hist[(t + 1) & 1], y, t, self.ngram, self.ban, self.nban,
+                      parent=parents if t > 0 else None, ignore=self.ignore, R=self.BK)
 
     # ------------------------------------------------------------------ prefill
     def prefill(self, cls_tok, feats, pos, sep_tok, mask_id):
@@ -162,16 +183,35 @@ class Generator:
         Vp = (V + 7) // 8 * 8
         logits = self._buf("logits", (BK, Vp), f32)
         self._linear(tt, "enc.txt_embeddings.word_embeddings.weight", eng.p["mlm.predictions.bias"], logits, BK, V, H, EPI_BIAS, ldc=Vp)
-        vals, idx = ops.logprob_topk(logits, k, R=BK, V=V, ld=Vp, eos_penalty_id=eos_pen)
+        if self.ngram:
+            vals, idx = ops.logprob_topk_banned(logits, k, R=BK, V=V, ld=Vp, eos_penalty_id=eos_pen, ban=self.ban, nban=self.nban)
+        else:
+            vals, idx = ops.logprob_topk(logits, k, R=BK, V=V, ld=Vp, eos_penalty_id=eos_pen)
         return vals, idx, logits[:, :V]
 
 
 @torch.no_grad()
 def generate(model, cls_tok, input_img, sep_tok, max_len=254, beam_size=1, min_len=0, length_penalty=0.0, eos_id=102, mask_id=103,
-             forced_ids=None, return_traces=False, forbid_duplicate_ngrams=False, forbid_ignore_set=None):
-    """See CXRBERT.generate."""
+             forced_ids=None, return_traces=False, forbid_duplicate_ngrams=False, forbid_ignore_set=None, no_repeat_ngram_size=0,
+             no_repeat_ignore_ids=None):
+    """See CXRBERT.generate.
+
+    n-gram blocking: the reference's `forbid_duplicate_ngrams=True, ngram_size=n, forbid_ignore_set=S` is spelled
+    `no_repeat_ngram_size=n, no_repeat_ignore_ids=S` here (n in 2..8, S an iterable of token ids, at most 256); the reference's own
+    keyword names are refused.  With blocking on, beam_size=1 runs the beam search at K = 1 (the reference's beam_search, which is
+    where its rule lives; its separate greedy loop ignores the flags) and returns what a beam call returns."""
     if forbid_duplicate_ngrams or forbid_ignore_set:
-        raise NotImplementedError("forbid_duplicate_ngrams / forbid_ignore_set depend on tokenizer words and are not supported")
+        raise NotImplementedError("forbid_duplicate_ngrams / ngram_size / forbid_ignore_set are spelled no_repeat_ngram_size=n / "
+                                  "no_repeat_ignore_ids=S here")
+    ngram = int(no_repeat_ngram_size or 0)
+    ignore_ids = sorted({int(i) for i in no_repeat_ignore_ids}) if no_repeat_ignore_ids is not None else []
+    if ngram:
+        if not NGRAM_MIN <= ngram <= NGRAM_MAX:
+            raise ValueError(f"no_repeat_ngram_size must be 0 (off) or in {NGRAM_MIN}..{NGRAM_MAX}")
+        if forced_ids is not None:
+            raise ValueError("forced_ids (teacher-forced scoring) cannot be combined with no_repeat_ngram_size")
+        if len(ignore_ids) > NGRAM_MAX_IGNORE:
+            raise ValueError(f"no_repeat_ignore_ids holds more than {NGRAM_MAX_IGNORE} ids")
     eng, cfg = model.engine, model.cfg
     if eng.device.type != "cuda":
         raise RuntimeError("medvill HIP kernels need CUDA(ROCm) tensors; there is no CPU fallback")
@@ -186,6 +226,8 @@ def generate(model, cls_tok, input_img, sep_tok, max_len=254, beam_size=1, min_l
     max_len = int(max_len)
     if not 1 <= max_len <= cfg.max_pos:
         raise ValueError(f"max_len must be in 1..max_position_embeddings ({cfg.max_pos})")
+    if ngram and max_len > NGRAM_MAX_LEN:
+        raise ValueError(f"no_repeat_ngram_size needs max_len <= {NGRAM_MAX_LEN}")
     feats, pos = model._regions(input_img)
     B, N = int(feats.shape[0]), int(feats.shape[1])
     if forced_ids is not None and forced_ids.shape[0] != B:
@@ -202,7 +244,9 @@ def generate(model, cls_tok, input_img, sep_tok, max_len=254, beam_size=1, min_l
         gen.prefill(cls_tok, feats, pos, sep_tok, mask_id)
         eng.keep_acts = prev[1]
         dev = eng.device
-        if K == 1:
+        if ngram:
+            gen.ngram_on(ngram, ignore_ids)
+        if K == 1 and not ngram:
             ids = torch.full((B, max_len), PAD_ID, dtype=torch.int64, device=dev)
             logp = torch.zeros((B, max_len), dtype=torch.float32, device=dev)
             step_logits = torch.empty((B, max_len, cfg.vocab_size), dtype=torch.float32, device=dev) if forced_ids is not None else None
@@ -232,8 +276,11 @@ def generate(model, cls_tok, input_img, sep_tok, max_len=254, beam_size=1, min_l
         for t in range(max_len):
             vals, idx, _ = gen.step(t, y, mask_id, K, eos_id if t < min_len else -1)
             back, k_ids = bs.step(vals, idx)
-            reorder_slot_table(gen.tbl, bs.parents(back), gen.n2, gen.n2 + t)
+            parents = bs.parents(back)
+            reorder_slot_table(gen.tbl, parents, gen.n2, gen.n2 + t)
             y = k_ids.reshape(-1)
+            if ngram and t + 1 < max_len:
+                gen.ngram_update(t, parents, y)
             if (t & 7) == 7 and bool(bs.all_done()):
                 break
         out, scores, traces = bs.finalize(max_len, PAD_ID)

@@ -644,6 +644,45 @@ def logprob_topk(logits, k, *, R=None, V=None, ld=None, eos_penalty_id=-1, vals=
     return vals, idx
 
 
+def ngram_ban(hist_in, hist_out, y, length, n, ban, nban, *, parent=None, ignore=None, R=None):
+    """One beam step of n-gram blocking (see mv_ngram_ban): hist_out[r, :length] = hist_in[parent[r], :length], hist_out[r, length] =
+    y[r]; ban[r, :nban[r]] = the words that would close a repeated n-gram of the new history, ascending.  hist_* / ban / nban / ignore
+    int32, y / parent int64 (parent None: identity).  Nothing is read back."""
+    L.require_cuda(hist_in, hist_out, y, ban, nban, parent, ignore)
+    if any(t.dtype != torch.int32 for t in (hist_in, hist_out, ban, nban)) or (ignore is not None and ignore.dtype != torch.int32):
+        raise TypeError("ngram_ban: histories, ban lists, counts and ignore ids are int32")
+    if y.dtype != torch.int64 or (parent is not None and parent.dtype != torch.int64):
+        raise TypeError("ngram_ban: y and parent are int64")
+    if hist_in.stride(0) != hist_out.stride(0):
+        raise ValueError("ngram_ban: the two histories share a leading dimension")
+    R = R if R is not None else y.shape[0]
+    rc = _lib().mv_ngram_ban(L.ptr(hist_in), L.ptr(hist_out), hist_in.stride(0), L.ptr(parent), L.ptr(y), R, int(length), int(n),
+                             L.ptr(ignore), 0 if ignore is None else ignore.numel(), L.ptr(ban), ban.stride(0), L.ptr(nban), L.stream_ptr())
+    L.check(rc, f"mv_ngram_ban(R={R},len={length},n={n})")
+    return hist_out, ban, nban
+
+
+def logprob_topk_banned(logits, k, *, R=None, V=None, ld=None, eos_penalty_id=-1, ban=None, nban=None, vals=None, idx=None, lse=None):
+    """logprob_topk with -10000 added to the log-prob of every word in ban[r, :nban[r]] (int32) after the normalisation and before the
+    EOS rule (see mv_logprob_topk_banned).  ban None: the bits logprob_topk gives."""
+    L.require_cuda(logits, vals, idx, lse, ban, nban)
+    if logits.dtype != torch.float32:
+        raise TypeError("logprob_topk_banned: f32 logits")
+    if any(t is not None and t.dtype != torch.int32 for t in (ban, nban)):
+        raise TypeError("logprob_topk_banned: ban lists and counts are int32")
+    R = R if R is not None else logits.shape[0]
+    V = V if V is not None else logits.shape[-1]
+    ld = ld if ld is not None else logits.stride(0)
+    if vals is None:
+        vals = torch.empty((R, k), dtype=torch.float32, device=logits.device)
+    if idx is None:
+        idx = torch.empty((R, k), dtype=torch.int64, device=logits.device)
+    rc = _lib().mv_logprob_topk_banned(L.ptr(logits), ld, R, V, int(k), int(eos_penalty_id), L.ptr(ban), 0 if ban is None else ban.stride(0),
+                                       L.ptr(nban), L.ptr(vals), L.ptr(idx), L.ptr(lse), L.stream_ptr())
+    L.check(rc, f"mv_logprob_topk_banned(R={R},V={V},k={k})")
+    return vals, idx
+
+
 def embed_rows(ids, pos, seg, E, P, Ty, gamma, beta, out, *, R, H, V, maxpos, eps, ntype=None, ldo=None):
     """out[r] = LN(E[ids[r]] + Ty[seg[r]] + P[pos[r]]) (int64 indices; see mv_embed_rows)."""
     L.require_cuda(ids, pos, seg, E, P, Ty, gamma, beta, out)

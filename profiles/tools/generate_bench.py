@@ -1,7 +1,11 @@
 """Timing of KV-cached report generation (CXRBERT.generate) on BERT-base, N = 180 regions, max_len 254: prefill and per-token decode at
 B in {1, 8, 64} x beam {1, 4}, after a warm-up, with HIP events; achieved bandwidth against the byte model of DESIGN.md "Generation";
 and, as the baseline, the same greedy generation by one full CXRBERT.forward per step (s2s mask, every step recomputed).
-usage: python profiles/tools/generate_bench.py [--batches 1,8,64] [--beams 1,4] [--max-len 254] [--recompute-steps 16] -> one JSON line"""
+--no-repeat-ngram n times the same decode steps once more with n-gram blocking on: every step followed by the history /
+ban-list update (mv_ngram_ban) and read through mv_logprob_topk_banned, on histories of a few words (so that every beam has bans);
+--repeats r times every loop r times, so that the spread of the unblocked step is known before the two are compared.
+usage: python profiles/tools/generate_bench.py [--batches 1,8,64] [--beams 1,4] [--max-len 254] [--recompute-steps 16]
+       [--no-repeat-ngram 3 --repeats 5] -> one JSON line"""
 import argparse
 import json
 import os
@@ -33,6 +37,8 @@ def main():
     ap.add_argument("--max-len", type=int, default=254)
     ap.add_argument("--steps", type=int, default=32, help="decode steps timed per configuration (after 4 warm-up steps)")
     ap.add_argument("--recompute-steps", type=int, default=16)
+    ap.add_argument("--no-repeat-ngram", type=int, default=0, help="also time the decode steps with n-gram blocking of this size")
+    ap.add_argument("--repeats", type=int, default=1, help="timed repetitions of every decode loop")
     a = ap.parse_args()
     torch.manual_seed(0)
     cd = dict(vocab_size=30522, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
@@ -64,14 +70,36 @@ def main():
                 # steady decode steps at the mean history length of a 254-token report (t around max_len / 2)
                 t0 = a.max_len // 2
                 torch.cuda.synchronize()
-                ms, _ = timed(lambda: [gen.step(t0 + i, y, MASK, K, -1) for i in range(a.steps)])
+                reps = [timed(lambda: [gen.step(t0 + i, y, MASK, K, -1) for i in range(a.steps)])[0] / a.steps for _ in range(a.repeats)]
+                blocked = []
+                if a.no_repeat_ngram:
+                    gen.ngram_on(a.no_repeat_ngram, [])
+                    words = torch.randint(1000, 1012, (B * K, a.max_len), generator=g).to(torch.int32).to(eng.device)
+                    gen.hist[0].copy_(words)
+                    gen.hist[1].copy_(words)
+                    parents = torch.arange(B * K, dtype=torch.int64, device=eng.device)
+
+                    def blocked_steps():
+                        for i in range(a.steps):
+                            gen.step(t0 + i, y, MASK, K, -1)
+                            gen.ngram_update(t0 + i, parents, y)
+                    blocked_steps()
+                    torch.cuda.synchronize()
+                    blocked = [timed(blocked_steps)[0] / a.steps for _ in range(a.repeats)]
+                    nban_mean = float(gen.nban.float().mean())
+                    gen.ngram = 0
             eng.training, eng.keep_acts = prev
-            per = ms / a.steps
+            per = sorted(reps)[len(reps) // 2]
             keys = N + 2 + t0
             kv_bytes = 2 * B * K * keys * 2 * H * cfg.layers * 2          # two rows per beam, K and V, 16-bit
             run = {"B": B, "beam": K, "prefill_ms": t_pre, "decode_ms_per_token": per, "tokens_per_s": B * 1e3 / per,
                    "mean_keys": keys, "achieved_GBps": (wbytes + kv_bytes) / (per * 1e-3) / 1e9,
                    "modelled_ms_per_token": (wbytes + kv_bytes) / 6e12 * 1e3}
+            if a.repeats > 1:
+                run["decode_ms_per_token_repeats"] = reps
+            if blocked:
+                run.update(no_repeat_ngram=a.no_repeat_ngram, blocked_ms_per_token=sorted(blocked)[len(blocked) // 2],
+                           blocked_ms_per_token_repeats=blocked, mean_banned_words=nban_mean)
             if K == 1 and a.recompute_steps > 0:
                 # baseline: greedy by full forward recompute, s2s mask over the whole prefix + text so far, every step
                 def recompute():
