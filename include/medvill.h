@@ -193,8 +193,10 @@ int mv_mask_build(const int32_t* desc, int B, int L, uint32_t* bits, uint8_t* ti
  * mv_mlm_draws: the two random sources of random_word for every token, from a counter-based hash of `key`:
  *   u   f32   [B,S]  stand-in for random.random(), on a 2^-24 grid in [0,1)
  *   rnd int32 [B,S]  stand-in for random.randrange(vocab)
+ *   token (b, t) draws from hash counters 2i and 2i+1, i = b*S + t; B*S <= 2^31-1 (MV_E_SHAPE above)
  * mv_mlm_corrupt consumes draws (these or the caller's own) and raw, un-corrupted ids:
- *   ids     int64 [B,S]   token ids; row b is valid for t < lengths[b] (1 <= lengths[b] <= S; out-of-range is clamped)
+ *   ids     int64 [B,S]   token ids; row b is valid for t < lengths[b] (1 <= lengths[b] <= S; out-of-range is clamped to 0..S, and a
+ *                         clamped length of 0 gives [SEP] at t = 0, no label, counts = 0 and n_ids = 1)
  *   family  int32 [B]     attention-mask family per sample for `desc` (see mv_mask_build); NULL = 0 (full)
  * outputs, in the reference's batch protocol (dataset_origin.py:181):
  *   input_txt  int64 [B,T]  T = S+1: corrupted ids, [SEP]=102 at t = lengths[b], [PAD]=0 after
@@ -257,8 +259,11 @@ int mv_pack_plan(const int32_t* desc, int B, int L, int32_t* cu, int32_t* rowmap
  *   perm    int32 [cu[B]]  packed row (old order) held by row i of the new order
  *   newpos  int32 [cu[B]]  its inverse
  *   qlim    int32 [B]      number of consumed rows of sample b (they are rows cu[b] .. cu[b]+qlim[b]-1 of the new order, ascending old order)
- *   sel_new int32 [n_sel]  newpos[sel[i]]
- * L: the logical sequence length (an upper bound of every sample's row count, <= 2048).  */
+ *   sel_new int32 [n_sel]  newpos[sel[i]] for 0 <= sel[i] < cu[B]; -1 for an entry that lies in no sample (a negative one, such as the
+ *                          -1 `inv` holds for a dropped position, or one >= cu[B]): the "no such row" of mv_gather_rows /
+ *                          mv_scatter_rows.  The kernel writes every entry; the caller pre-fills nothing.
+ * Entries of sel in no sample select nothing; duplicates count once in qlim.  perm / newpos from cu[B] on are not written.
+ * L: the logical sequence length (an upper bound of every sample's row count, <= 2048; MV_E_SHAPE above).  */
 int mv_tail_perm(const int32_t* cu, int B, int L, const int32_t* sel, int n_sel, int32_t* perm, int32_t* newpos, int32_t* qlim,
                  int32_t* sel_new, void* stream);
 

@@ -149,6 +149,8 @@ __global__ __launch_bounds__(NT) void pack_plan_kernel(const int32_t* __restrict
 
 // Row order of the last encoder layer: within every sample the rows the heads consume (`sel`: labelled rows + first rows) come first,
 // in ascending order, then the others.  One block per sample; wave 0 assigns positions with ballots (stable partition).
+// An entry of sel that lies in no sample (-1 for a position mv_pack_plan dropped, or >= cu[B]) gets sel_new = -1: the entries below
+// cu[0] are block 0's, those from cu[B] on the last block's, so every sel_new[i] has exactly one writer.
 #define TP_MAXL 2048
 __global__ __launch_bounds__(NT) void tail_perm_kernel(const int32_t* __restrict__ cu, const int32_t* __restrict__ sel, int n_sel,
                                                        int32_t* __restrict__ perm, int32_t* __restrict__ newpos,
@@ -181,9 +183,11 @@ __global__ __launch_bounds__(NT) void tail_perm_kernel(const int32_t* __restrict
   }
   __threadfence_block();
   __syncthreads();
+  const bool first = b == 0, last = b == (int)gridDim.x - 1;
   for (int i = threadIdx.x; i < n_sel; i += NT) {
-    const int r = sel[i] - lo;
-    if (r >= 0 && r < n) sel_new[i] = newpos[lo + r];
+    const int s = sel[i], r = s - lo;
+    if (s >= lo && r < n) sel_new[i] = newpos[lo + r];
+    else if ((first && s < lo) || (last && s >= lo + n)) sel_new[i] = -1;
   }
 }
 
@@ -211,6 +215,7 @@ extern "C" int mv_tail_perm(const int32_t* cu, int B, int L, const int32_t* sel,
 extern "C" int mv_mlm_draws(unsigned long long key, int B, int S, int vocab, float* u, int32_t* rnd, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!u || !rnd || B <= 0 || S <= 0 || vocab <= 0) return MV_E_ARG;
+  if ((long long)B * S > 0x7fffffffLL) return MV_E_SHAPE;
   const int n = B * S;
   mlm_draws_kernel<<<(n + 255) / 256, 256, 0, stream>>>((unsigned)(key & 0xffffffffULL), (unsigned)(key >> 32), n, vocab, u, rnd);
   MV_CHECK_LAUNCH();

@@ -135,7 +135,8 @@ def pack_plan(desc, B, Lq):
 
 
 def tail_perm(cu, B, Lq, sel, total_rows):
-    """(perm, newpos, qlim, sel_new) of mv_tail_perm: the last layer's row order with the consumed rows `sel` (packed row indices) first."""
+    """(perm, newpos, qlim, sel_new) of mv_tail_perm: the last layer's row order with the consumed rows `sel` (packed row indices) first.
+    sel_new is -1 where sel names no row (the -1 of a dropped position, or an index >= total_rows): the kernel writes every entry."""
     L.require_cuda(cu, sel)
     if cu.dtype != torch.int32 or sel.dtype != torch.int32:
         raise TypeError("tail_perm: int32 tensors")

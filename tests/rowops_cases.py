@@ -849,18 +849,30 @@ def dm_threshold(p):
     return 0 if p <= 0 else min(65535, int(np.float32(p) * np.float32(65536.0) + np.float32(0.5)))
 
 
+HASH_MUL = (0x9E3779B1, 0x85EBCA6B)          # mv_hash32 (csrc/mv_common.h): the two multipliers, the three xor-shifts
+HASH_SHIFT = (15, 13, 16)
+
+
+def hash32(x, key):
+    """mv_hash32(x, k0 = key & 0xffffffff, k1 = key >> 32) of csrc/mv_common.h for an array of 32-bit counters: uint64 arithmetic masked
+    to 32 bits after every multiply -> uint64 array of values < 2^32.  The one restatement of the hash in the tests: the hidden-state
+    dropout mask (dm_restated) and the MLM draws (tests/batch_cases.py) both come from here."""
+    m = np.uint64(0xffffffff)
+    x = np.asarray(x, dtype=np.uint64) & m
+    k0, k1 = np.uint64(int(key) & 0xffffffff), np.uint64((int(key) >> 32) & 0xffffffff)
+    x = ((x ^ k0) * np.uint64(HASH_MUL[0])) & m
+    x ^= x >> np.uint64(HASH_SHIFT[0])
+    x = ((x ^ k1) * np.uint64(HASH_MUL[1])) & m
+    x ^= x >> np.uint64(HASH_SHIFT[1])
+    x ^= x >> np.uint64(HASH_SHIFT[2])
+    return x
+
+
 def dm_restated(p, key, n):
     """The mask written out with numpy: one 32-bit hash per PAIR of elements (index >> 1), element i reads half i & 1."""
     thr = dm_threshold(p)
     i = np.arange(n, dtype=np.uint64)
-    x = (i >> np.uint64(1)).astype(np.uint32)
-    k0, k1 = np.uint32(key & 0xffffffff), np.uint32(key >> 32)
-    with np.errstate(over="ignore"):
-        x = (x ^ k0) * np.uint32(0x9E3779B1)
-        x ^= x >> np.uint32(15)
-        x = (x ^ k1) * np.uint32(0x85EBCA6B)
-        x ^= x >> np.uint32(13)
-        x ^= x >> np.uint32(16)
+    x = hash32(i >> np.uint64(1), key).astype(np.uint32)
     half = (x >> (np.uint32(16) * (i & np.uint64(1)).astype(np.uint32))) & np.uint32(0xffff)
     return (half >= thr).astype(np.uint8) if thr else np.ones(n, dtype=np.uint8)
 
