@@ -16,7 +16,7 @@
 // K/V (or Q/dO) tiles of 64 rows x 64 dh live in LDS in ONE image that serves both the
 // row reads (ds_read_b128) and the transposed reads (ds_read_b64_tr_b16), conflict-free for both.
 // The VALU kernels below them are the exact-fp32 path and the on-GPU cross-check.
-#include "mv_common.h"
+#include "mv_dispatch.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // Timing experiments on the forward kernel (profiles/tools/attn_ablate.sh builds variant libraries with -DATT_ABL=<bits>; results are
@@ -1661,6 +1661,23 @@ extern "C" int mv_attn_dropmask(float p_drop, unsigned long long drop_key, int B
   return MV_OK;
 }
 
+typedef mv_types<bf16_t, f16_t> MfmaAccept;      // the MFMA kernels take both 16-bit encodings as bf16_t pointers; <F16> picks the MFMA
+
+// what mv_attn_fwd and mv_attn_bwd both put into the MFMA kernels' arguments
+static AttnArgs attn_args(const void* qkv, const uint32_t* bits, const uint8_t* tileinfo, int B, int L, int A, int dh, size_t bytes_qkv, float p_drop,
+                          const uint32_t* dropbits, const int32_t* cu, const int32_t* qlim) {
+  AttnArgs a{};
+  a.cu = cu; a.qlim = qlim; a.order = mv_knob(MV_KNOB_ATTN_ORDER);
+  a.qkv = (const bf16_t*)qkv; a.bits = bits; a.info = tileinfo;
+  a.B = B; a.L = L; a.A = A; a.H = A * dh; a.W = (L + 31) / 32; a.T = (L + 63) / 64;
+  a.scale = 1.0f / sqrtf((float)dh);
+  a.bytes_qkv = (unsigned)bytes_qkv;
+  a.drop_on = p_drop > 0.f; a.inv_keep = attn_inv_keep(p_drop);
+  a.dropbits = a.drop_on ? dropbits : nullptr; a.bytes_dbits = (unsigned)(dropbits_words(B, L, A) * 4);
+  a.NQB = (L + 31) / 32; a.NKT = (L + 63) / 64;
+  return a;
+}
+
 template <typename T>
 static int launch_simple_fwd(const void* qkv, const uint32_t* bits, void* ctx, float* lse, int B, int L, int A, int dh, float p_drop,
                              const uint32_t* dropbits, hipStream_t stream) {
@@ -1691,34 +1708,24 @@ extern "C" int mv_attn_fwd(int dtype, const void* qkv, const uint32_t* bits, con
     const size_t nrow = cu ? (size_t)total_rows : (size_t)B * L;
     const size_t bq = nrow * 3 * H * 2;
     if (bq >= 0x7fffffffULL || (((uintptr_t)qkv) & 15) || (((uintptr_t)ctx) & 7) || (((uintptr_t)ctx_bf16) & 7)) return MV_E_SHAPE;
-    AttnArgs a{};
-    a.cu = cu; a.qlim = qlim; a.order = mv_knob(MV_KNOB_ATTN_ORDER);
-    a.qkv = (const bf16_t*)qkv; a.out = (bf16_t*)ctx; a.out2 = (bf16_t*)ctx_bf16; a.bits = bits; a.info = tileinfo; a.lse = lse;
-    a.B = B; a.L = L; a.A = A; a.H = H; a.W = (L + 31) / 32; a.T = (L + 63) / 64;
-    a.scale = 1.0f / sqrtf((float)dh);
-    a.bytes_qkv = (unsigned)bq;
-    a.drop_on = p_drop > 0.f; a.inv_keep = attn_inv_keep(p_drop);
-    a.dropbits = a.drop_on ? dropbits : nullptr; a.bytes_dbits = (unsigned)(dropbits_words(B, L, A) * 4);
-    a.NQB = (L + 31) / 32; a.NKT = (L + 63) / 64;
+    AttnArgs a = attn_args(qkv, bits, tileinfo, B, L, A, dh, bq, p_drop, dropbits, cu, qlim);
+    a.out = (bf16_t*)ctx; a.out2 = (bf16_t*)ctx_bf16; a.lse = lse;
     static bool attr = false;
     if (!attr) {
       (void)hipFuncSetAttribute((const void*)attn_fwd_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FWD_NS * 16384);
       (void)hipFuncSetAttribute((const void*)attn_fwd_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FWD_NS * 16384);
       attr = true;
     }
-    if (dtype == MV_F16) hipLaunchKernelGGL(attn_fwd_mfma_kernel<true>, dim3((L + 127) / 128, A, B), dim3(256), FWD_NS * 16384, stream, a);
-    else hipLaunchKernelGGL(attn_fwd_mfma_kernel<false>, dim3((L + 127) / 128, A, B), dim3(256), FWD_NS * 16384, stream, a);
-    MV_CHECK_LAUNCH();
-    return MV_OK;
+    return mv_with_type(dtype, MfmaAccept{}, [&](auto t) -> int {
+      hipLaunchKernelGGL(attn_fwd_mfma_kernel<decltype(t)::code == MV_F16>, dim3((L + 127) / 128, A, B), dim3(256), FWD_NS * 16384, stream, a);
+      return (int)hipGetLastError();
+    });
   }
   if (dh > 128 || cu || qlim) return MV_E_SHAPE;       // packed rows / query limits: MFMA kernels only
-  if (dtype == MV_F16) {                         // VALU cross-check of the f16 forward (mv_set_impl(1))
-    int rc = launch_simple_fwd<f16_t>(qkv, bits, ctx, lse, B, L, A, dh, p_drop, dropbits, stream);
-    if (rc == MV_OK && ctx_bf16) rc = mv_cast(ctx, MV_F16, ctx_bf16, MV_BF16, (size_t)B * L * H, stream_);
-    return rc;
-  }
-  return dtype == MV_F32 ? launch_simple_fwd<float>(qkv, bits, ctx, lse, B, L, A, dh, p_drop, dropbits, stream)
-                         : launch_simple_fwd<bf16_t>(qkv, bits, ctx, lse, B, L, A, dh, p_drop, dropbits, stream);
+  int rc = mv_with_type(dtype, [&](auto t) { return launch_simple_fwd<MV_T(t)>(qkv, bits, ctx, lse, B, L, A, dh, p_drop, dropbits, stream); });
+  // VALU cross-check of the f16 forward (mv_set_impl(1)): ctx_bf16 comes with MV_F16 only (checked above)
+  if (rc == MV_OK && ctx_bf16) rc = mv_cast(ctx, MV_F16, ctx_bf16, MV_BF16, (size_t)B * L * H, stream_);
+  return rc;
 }
 
 template <typename T>
@@ -1757,17 +1764,11 @@ extern "C" int mv_attn_bwd(int dtype, const void* qkv, const void* ctx, const vo
     const size_t nrow = cu ? (size_t)total_rows : (size_t)B * L;
     const size_t bq = nrow * 3 * H * 2, bc = nrow * H * 2;
     if (bq >= 0x7fffffffULL || (((uintptr_t)qkv) & 15) || (((uintptr_t)dctx) & 15) || (((uintptr_t)dqkv) & 7)) return MV_E_SHAPE;
-    AttnArgs a{};
-    a.cu = cu; a.qlim = qlim; a.order = mv_knob(MV_KNOB_ATTN_ORDER);
-    a.qkv = (const bf16_t*)qkv; a.ctx = (const bf16_t*)ctx; a.dctx = (const bf16_t*)dctx; a.dqkv = (bf16_t*)dqkv;
-    a.bits = bits; a.info = tileinfo; a.lse_in = lse; a.delta = delta; a.delta_out = delta;
-    a.B = B; a.L = L; a.A = A; a.H = H; a.W = (L + 31) / 32; a.T = (L + 63) / 64;
-    a.scale = 1.0f / sqrtf((float)dh);
-    a.bytes_qkv = (unsigned)bq; a.bytes_ctx = (unsigned)bc;
+    AttnArgs a = attn_args(qkv, bits, tileinfo, B, L, A, dh, bq, p_drop, dropbits, cu, qlim);
+    a.ctx = (const bf16_t*)ctx; a.dctx = (const bf16_t*)dctx; a.dqkv = (bf16_t*)dqkv;
+    a.lse_in = lse; a.delta = delta; a.delta_out = delta;
+    a.bytes_ctx = (unsigned)bc;
     a.bytes_stat = (unsigned)((size_t)B * A * L * 4); a.bytes_bits = (unsigned)((size_t)B * L * a.W * 4);
-    a.drop_on = p_drop > 0.f; a.inv_keep = attn_inv_keep(p_drop);
-    a.dropbits = a.drop_on ? dropbits : nullptr; a.bytes_dbits = (unsigned)(dropbits_words(B, L, A) * 4);
-    a.NQB = (L + 31) / 32; a.NKT = (L + 63) / 64;
     static bool attr = false;
     if (!attr) {
       (void)hipFuncSetAttribute((const void*)attn_bwd_dq_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_NS * 16384);
@@ -1777,18 +1778,17 @@ extern "C" int mv_attn_bwd(int dtype, const void* qkv, const void* ctx, const vo
       attr = true;
     }
     dim3 grid((L + 127) / 128, A, B);
-    if (dtype == MV_F16) hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel<true>, grid, dim3(256), DQ_NS * 16384, stream, a);
-    else hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel<false>, grid, dim3(256), DQ_NS * 16384, stream, a);
-    MV_CHECK_LAUNCH();
-    if (dtype == MV_F16) hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<true>, grid, dim3(256), DKV_NS * KV_STAGE, stream, a);
-    else hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<false>, grid, dim3(256), DKV_NS * KV_STAGE, stream, a);
-    MV_CHECK_LAUNCH();
-    return MV_OK;
+    return mv_with_type(dtype, MfmaAccept{}, [&](auto t) -> int {
+      hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel<decltype(t)::code == MV_F16>, grid, dim3(256), DQ_NS * 16384, stream, a);
+      MV_CHECK_LAUNCH();
+      hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<decltype(t)::code == MV_F16>, grid, dim3(256), DKV_NS * KV_STAGE, stream, a);
+      return (int)hipGetLastError();
+    });
   }
   if (dh > 128 || cu || qlim) return MV_E_SHAPE;
-  if (dtype == MV_F16) return launch_simple_bwd<f16_t>(qkv, ctx, dctx, lse, bits, dqkv, delta, B, L, A, dh, p_drop, dropbits, stream);
-  return dtype == MV_F32 ? launch_simple_bwd<float>(qkv, ctx, dctx, lse, bits, dqkv, delta, B, L, A, dh, p_drop, dropbits, stream)
-                         : launch_simple_bwd<bf16_t>(qkv, ctx, dctx, lse, bits, dqkv, delta, B, L, A, dh, p_drop, dropbits, stream);
+  return mv_with_type(dtype, [&](auto t) {
+    return launch_simple_bwd<MV_T(t)>(qkv, ctx, dctx, lse, bits, dqkv, delta, B, L, A, dh, p_drop, dropbits, stream);
+  });
 }
 
 template <typename T, typename TO>
@@ -1807,6 +1807,8 @@ static int launch_simple_probs(const void* qkv, const uint32_t* bits, const floa
 
 extern "C" int mv_attn_probs(int dtype, const void* qkv, const uint32_t* bits, const uint8_t* tileinfo, const float* lse, void* probs,
                              int out_dtype, int B, int L, int A, int dh, float p_drop, const uint32_t* dropbits, int head_mean, void* stream_) {
+  // (dtype of qkv, out_dtype): f32 probabilities, or qkv's encoding -- any other out_dtype is MV_E_ARG, refused below
+  typedef mv_pairs<mv_pair<float, float>, mv_pair<bf16_t, float>, mv_pair<bf16_t, bf16_t>, mv_pair<f16_t, float>, mv_pair<f16_t, f16_t>> Accept;
   hipStream_t stream = (hipStream_t)stream_;
   if (!qkv || !bits || !tileinfo || !lse || !probs || B <= 0 || L <= 0 || A <= 0 || dh <= 0) return MV_E_ARG;
   if (!mv_dtype_ok(dtype)) return MV_E_DTYPE;
@@ -1834,21 +1836,13 @@ extern "C" int mv_attn_probs(int dtype, const void* qkv, const uint32_t* bits, c
     a.vec = (L % (o32 ? 4 : 8)) == 0;
     a.order = mv_knob(MV_KNOB_ATTN_ORDER);
     const dim3 grid(Tt, head_mean ? 1 : A, B);
-    if (dtype == MV_F16) {
-      if (o32) hipLaunchKernelGGL((attn_probs_mfma_kernel<true, float>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((attn_probs_mfma_kernel<true, f16_t>), grid, dim3(256), 0, stream, a);
-    } else {
-      if (o32) hipLaunchKernelGGL((attn_probs_mfma_kernel<false, float>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((attn_probs_mfma_kernel<false, bf16_t>), grid, dim3(256), 0, stream, a);
-    }
-    MV_CHECK_LAUNCH();
-    return MV_OK;
+    return mv_with_types(dtype, out_dtype, Accept{}, [&](auto t, auto to) -> int {      // (f32 qkv never comes here: mv_is16 above)
+      hipLaunchKernelGGL((attn_probs_mfma_kernel<decltype(t)::code == MV_F16, MV_T(to)>), grid, dim3(256), 0, stream, a);
+      return (int)hipGetLastError();
+    });
   }
   if (dh > 128) return MV_E_SHAPE;
-  if (dtype == MV_F32) return launch_simple_probs<float, float>(qkv, bits, lse, probs, B, L, A, dh, p_drop, dropbits, head_mean, stream);
-  if (dtype == MV_F16)
-    return o32 ? launch_simple_probs<f16_t, float>(qkv, bits, lse, probs, B, L, A, dh, p_drop, dropbits, head_mean, stream)
-               : launch_simple_probs<f16_t, f16_t>(qkv, bits, lse, probs, B, L, A, dh, p_drop, dropbits, head_mean, stream);
-  return o32 ? launch_simple_probs<bf16_t, float>(qkv, bits, lse, probs, B, L, A, dh, p_drop, dropbits, head_mean, stream)
-             : launch_simple_probs<bf16_t, bf16_t>(qkv, bits, lse, probs, B, L, A, dh, p_drop, dropbits, head_mean, stream);
+  return mv_with_types(dtype, out_dtype, Accept{}, [&](auto t, auto to) {
+    return launch_simple_probs<MV_T(t), MV_T(to)>(qkv, bits, lse, probs, B, L, A, dh, p_drop, dropbits, head_mean, stream);
+  });
 }

@@ -4,7 +4,7 @@
 // the CNN (cxrbert_origin.py:66-70 unfreezes `children()[5:]` of a module that has a single child), so only the forward
 // exists -- in both BatchNorm modes: batch statistics (model.train()) and running statistics (eval()).
 // All kernels here are HBM-bound byte movers: coalesced 16-byte accesses along the channel dimension, no LDS tiling.
-#include "mv_common.h"
+#include "mv_dispatch.h"
 
 namespace {
 
@@ -172,18 +172,20 @@ inline bool aligned4(const void* p, int dtype) { return (((uintptr_t)p) & (dtype
 }  // namespace
 
 extern "C" int mv_nchw_to_nhwc(const float* src, void* dst, int dst_dtype, int B, int C, int H, int W, int Cp, void* stream_) {
+  typedef mv_types<float, bf16_t> Accept;
   hipStream_t stream = (hipStream_t)stream_;
   if (!src || !dst || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Cp < C) return MV_E_ARG;
   const size_t n = (size_t)B * H * W * Cp;
-  if (dst_dtype == MV_BF16) nchw_to_nhwc_kernel<bf16_t><<<grid_for(n), 256, 0, stream>>>(src, (bf16_t*)dst, B, C, H, W, Cp);
-  else if (dst_dtype == MV_F32) nchw_to_nhwc_kernel<float><<<grid_for(n), 256, 0, stream>>>(src, (float*)dst, B, C, H, W, Cp);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dst_dtype, Accept{}, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    nchw_to_nhwc_kernel<T><<<grid_for(n), 256, 0, stream>>>(src, (T*)dst, B, C, H, W, Cp);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int mv_im2col(int dtype, const void* src, int B, int H, int W, int C, int kh, int kw, int stride, int pad, void* dst,
                          int ldk, void* stream_) {
+  typedef mv_types<float, bf16_t> Accept;
   hipStream_t stream = (hipStream_t)stream_;
   if (!src || !dst || B <= 0 || H <= 0 || W <= 0 || C <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return MV_E_ARG;
   if (ldk < kh * kw * C) return MV_E_SHAPE;
@@ -191,33 +193,36 @@ extern "C" int mv_im2col(int dtype, const void* src, int B, int H, int W, int C,
   if (Ho <= 0 || Wo <= 0) return MV_E_SHAPE;
   const bool vec = dtype == MV_BF16 && (C & 7) == 0 && (ldk & 7) == 0 && ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0;
   const size_t rows = (size_t)B * Ho * Wo;
-  if (dtype == MV_BF16) {
-    if (vec) im2col_kernel<bf16_t, 8><<<grid_for(rows * (ldk / 8)), 256, 0, stream>>>((const bf16_t*)src, (bf16_t*)dst, B, H, W, C, Ho, Wo, kh, kw, stride, pad, ldk);
-    else im2col_kernel<bf16_t, 4><<<grid_for(rows * ((ldk + 3) / 4)), 256, 0, stream>>>((const bf16_t*)src, (bf16_t*)dst, B, H, W, C, Ho, Wo, kh, kw, stride, pad, ldk);
-  } else if (dtype == MV_F32) {
-    im2col_kernel<float, 4><<<grid_for(rows * ((ldk + 3) / 4)), 256, 0, stream>>>((const float*)src, (float*)dst, B, H, W, C, Ho, Wo, kh, kw, stride, pad, ldk);
-  } else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, Accept{}, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    if constexpr (sizeof(T) == 2) {      // the 8-wide gather exists for bf16 only
+      if (vec) {
+        im2col_kernel<T, 8><<<grid_for(rows * (ldk / 8)), 256, 0, stream>>>((const T*)src, (T*)dst, B, H, W, C, Ho, Wo, kh, kw, stride, pad, ldk);
+        return (int)hipGetLastError();
+      }
+    }
+    im2col_kernel<T, 4><<<grid_for(rows * ((ldk + 3) / 4)), 256, 0, stream>>>((const T*)src, (T*)dst, B, H, W, C, Ho, Wo, kh, kw, stride, pad, ldk);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int mv_col_stats(int dtype, const void* x, int ldx, int rows, int C, float* stats, void* stream_) {
+  typedef mv_types<float, bf16_t> Accept;
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !stats || rows <= 0 || C <= 0 || ldx < C) return MV_E_ARG;
   if ((C & 3) || (ldx & 3)) return MV_E_SHAPE;
-  if (dtype != MV_BF16 && dtype != MV_F32) return MV_E_DTYPE;      // before the memset: a refused call leaves stats alone
-  if (!aligned4(x, dtype)) return MV_E_SHAPE;
-  hipError_t e = hipMemsetAsync(stats, 0, sizeof(float) * 2 * (size_t)C, stream);
-  if (e != hipSuccess) return (int)e;
-  int slabs = (rows + 511) / 512;
-  if (slabs > 2048) slabs = 2048;
-  const int rpb = (rows + slabs - 1) / slabs;
-  dim3 grid((C + 63) / 64, (rows + rpb - 1) / rpb), block(256);
-  if (dtype == MV_BF16) col_stats_kernel<bf16_t><<<grid, block, 0, stream>>>((const bf16_t*)x, ldx, rows, C, stats, rpb);
-  else if (dtype == MV_F32) col_stats_kernel<float><<<grid, block, 0, stream>>>((const float*)x, ldx, rows, C, stats, rpb);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, Accept{}, [&](auto t) -> int {      // the memset is in here: a refused call leaves stats alone
+    typedef MV_T(t) T;
+    if (!aligned4(x, dtype)) return MV_E_SHAPE;
+    hipError_t e = hipMemsetAsync(stats, 0, sizeof(float) * 2 * (size_t)C, stream);
+    if (e != hipSuccess) return (int)e;
+    int slabs = (rows + 511) / 512;
+    if (slabs > 2048) slabs = 2048;
+    const int rpb = (rows + slabs - 1) / slabs;
+    dim3 grid((C + 63) / 64, (rows + rpb - 1) / rpb), block(256);
+    col_stats_kernel<T><<<grid, block, 0, stream>>>((const T*)x, ldx, rows, C, stats, rpb);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int mv_bn_finalize(const float* stats, int C, long long rows, float eps, float momentum, float* mean, float* rstd,
@@ -232,33 +237,33 @@ extern "C" int mv_bn_finalize(const float* stats, int C, long long rows, float e
 
 extern "C" int mv_bn_act(int dtype, const void* x, int x_dtype, const float* mean, const float* rstd, const float* gamma, const float* beta,
                          const void* residual, void* y, long long rows, int C, int relu, void* stream_) {
+  typedef mv_pairs<mv_pair<bf16_t, bf16_t>, mv_pair<bf16_t, float>, mv_pair<float, float>> Accept;      // (dtype of y and residual, x_dtype)
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !mean || !rstd || !gamma || !beta || !y || rows <= 0 || C <= 0) return MV_E_ARG;
   if (C & 3) return MV_E_SHAPE;
-  if (!((dtype == MV_BF16 && (x_dtype == MV_BF16 || x_dtype == MV_F32)) || (dtype == MV_F32 && x_dtype == MV_F32))) return MV_E_DTYPE;
-  if (!aligned4(x, x_dtype) || !aligned4(y, dtype) || !aligned4(residual, dtype) || !aligned4(mean, MV_F32) || !aligned4(rstd, MV_F32) ||
-      !aligned4(gamma, MV_F32) || !aligned4(beta, MV_F32))
-    return MV_E_SHAPE;
-  const size_t n = (size_t)rows * (C / 4);
-  if (dtype == MV_BF16 && x_dtype == MV_BF16) bn_act_kernel<bf16_t, bf16_t><<<grid_for(n), 256, 0, stream>>>((const bf16_t*)x, mean, rstd, gamma, beta, (const bf16_t*)residual, (bf16_t*)y, (size_t)rows, C, relu);
-  else if (dtype == MV_BF16 && x_dtype == MV_F32) bn_act_kernel<float, bf16_t><<<grid_for(n), 256, 0, stream>>>((const float*)x, mean, rstd, gamma, beta, (const bf16_t*)residual, (bf16_t*)y, (size_t)rows, C, relu);
-  else if (dtype == MV_F32 && x_dtype == MV_F32) bn_act_kernel<float, float><<<grid_for(n), 256, 0, stream>>>((const float*)x, mean, rstd, gamma, beta, (const float*)residual, (float*)y, (size_t)rows, C, relu);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_types(dtype, x_dtype, Accept{}, [&](auto ty, auto tx) -> int {
+    typedef MV_T(ty) TY;
+    typedef MV_T(tx) TX;
+    if (!aligned4(x, x_dtype) || !aligned4(y, dtype) || !aligned4(residual, dtype) || !aligned4(mean, MV_F32) || !aligned4(rstd, MV_F32) ||
+        !aligned4(gamma, MV_F32) || !aligned4(beta, MV_F32))
+      return MV_E_SHAPE;
+    const size_t n = (size_t)rows * (C / 4);
+    bn_act_kernel<TX, TY><<<grid_for(n), 256, 0, stream>>>((const TX*)x, mean, rstd, gamma, beta, (const TY*)residual, (TY*)y, (size_t)rows, C, relu);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int mv_maxpool3x3s2(int dtype, const void* x, void* y, int B, int H, int W, int C, void* stream_) {
+  typedef mv_types<float, bf16_t> Accept;
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0) return MV_E_ARG;
   if (C & 3) return MV_E_SHAPE;
-  if (dtype != MV_BF16 && dtype != MV_F32) return MV_E_DTYPE;
-  if (!aligned4(x, dtype) || !aligned4(y, dtype)) return MV_E_SHAPE;
-  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  const size_t n = (size_t)B * Ho * Wo * (C / 4);
-  if (dtype == MV_BF16) maxpool3x3s2_kernel<bf16_t><<<grid_for(n), 256, 0, stream>>>((const bf16_t*)x, (bf16_t*)y, B, H, W, C, Ho, Wo);
-  else if (dtype == MV_F32) maxpool3x3s2_kernel<float><<<grid_for(n), 256, 0, stream>>>((const float*)x, (float*)y, B, H, W, C, Ho, Wo);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, Accept{}, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    if (!aligned4(x, dtype) || !aligned4(y, dtype)) return MV_E_SHAPE;
+    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    const size_t n = (size_t)B * Ho * Wo * (C / 4);
+    maxpool3x3s2_kernel<T><<<grid_for(n), 256, 0, stream>>>((const T*)x, (T*)y, B, H, W, C, Ho, Wo);
+    return (int)hipGetLastError();
+  });
 }

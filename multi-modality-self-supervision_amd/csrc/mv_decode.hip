@@ -9,7 +9,7 @@
 //   mv_ngram_ban     one beam step of n-gram blocking: gather the parents' word histories, append the chosen word, list the words
 //                    that would repeat an n-gram
 //   mv_logprob_topk_banned   mv_logprob_topk with -10000 added to the log-prob of every listed word of the row
-#include "mv_common.h"
+#include "mv_dispatch.h"
 #include "mv_gemm_common.h"
 
 // ------------------------------------------------------------------------------------------------ mv_gemm_rows
@@ -98,32 +98,26 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict
   }
 }
 
-template <bool F16, int MT>
-static void launch_gemm_rows_ct(int c_dtype, dim3 grid, size_t lds, hipStream_t st, const bf16_t* x, int ldx, const bf16_t* W, int ldw,
-                                void* c, int ldc, const float* bias, int epi, const void* r, int ldr, int r_dtype, int M, int N, int K) {
-  if (c_dtype == MV_F32)
-    hipLaunchKernelGGL((gemm_rows_kernel<F16, MT, MV_F32>), grid, dim3(256), lds, st, x, ldx, W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K);
-  else if (c_dtype == MV_F16)
-    hipLaunchKernelGGL((gemm_rows_kernel<F16, MT, MV_F16>), grid, dim3(256), lds, st, x, ldx, W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K);
-  else
-    hipLaunchKernelGGL((gemm_rows_kernel<F16, MT, MV_BF16>), grid, dim3(256), lds, st, x, ldx, W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K);
-}
-
 template <bool F16>
-static void launch_gemm_rows(int mt, int c_dtype, dim3 grid, hipStream_t st, const bf16_t* x, int ldx, const bf16_t* W, int ldw, void* c,
-                             int ldc, const float* bias, int epi, const void* r, int ldr, int r_dtype, int M, int N, int K) {
+static int launch_gemm_rows(int mt, int c_dtype, dim3 grid, hipStream_t st, const bf16_t* x, int ldx, const bf16_t* W, int ldw, void* c,
+                            int ldc, const float* bias, int epi, const void* r, int ldr, int r_dtype, int M, int N, int K) {
   const size_t lds = (size_t)GR_WAVES * mt * 16 * GR_LDR * sizeof(float);
+  return mv_with_type(c_dtype, [&](auto tc) -> int {      // every output encoding, for either 16-bit operand encoding
+    constexpr int CT = decltype(tc)::code;
 #define GR_CASE(T_) \
-  case T_: launch_gemm_rows_ct<F16, T_>(c_dtype, grid, lds, st, x, ldx, W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K); break;
-  switch (mt) {
-    GR_CASE(1) GR_CASE(2) GR_CASE(3) GR_CASE(4) GR_CASE(5) GR_CASE(6) GR_CASE(7) GR_CASE(8)
-    GR_CASE(9) GR_CASE(10) GR_CASE(11) GR_CASE(12) GR_CASE(13) GR_CASE(14) GR_CASE(15) GR_CASE(16)
-  }
+  case T_: hipLaunchKernelGGL((gemm_rows_kernel<F16, T_, CT>), grid, dim3(256), lds, st, x, ldx, W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K); break;
+    switch (mt) {
+      GR_CASE(1) GR_CASE(2) GR_CASE(3) GR_CASE(4) GR_CASE(5) GR_CASE(6) GR_CASE(7) GR_CASE(8)
+      GR_CASE(9) GR_CASE(10) GR_CASE(11) GR_CASE(12) GR_CASE(13) GR_CASE(14) GR_CASE(15) GR_CASE(16)
+    }
 #undef GR_CASE
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int mv_gemm_rows(int dtype, int M, int N, int K, const void* x, int ldx, const void* W, int ldw, void* c, int ldc, int c_dtype,
                             const float* bias, int epi, const void* r, int ldr, int r_dtype, void* stream_) {
+  typedef mv_types<bf16_t, f16_t> Accept;      // of x and W; c_dtype is any of the three (launch_gemm_rows)
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !W || !c || M <= 0 || N <= 0 || K <= 0) return MV_E_ARG;
   if (!mv_is16(dtype) || !mv_dtype_ok(c_dtype)) return MV_E_DTYPE;
@@ -135,12 +129,10 @@ extern "C" int mv_gemm_rows(int dtype, int M, int N, int K, const void* x, int l
   if ((((uintptr_t)x) & 15) || (((uintptr_t)W) & 15)) return MV_E_SHAPE;
   const int mt = (M + 15) / 16;
   dim3 grid((N + GR_BN - 1) / GR_BN);
-  if (dtype == MV_F16)
-    launch_gemm_rows<true>(mt, c_dtype, grid, stream, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K);
-  else
-    launch_gemm_rows<false>(mt, c_dtype, grid, stream, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw, c, ldc, bias, epi, r, ldr, r_dtype, M, N, K);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, Accept{}, [&](auto t) {      // the kernel takes both operand encodings as bf16_t pointers; F16 picks the MFMA
+    return launch_gemm_rows<decltype(t)::code == MV_F16>(mt, c_dtype, grid, stream, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw, c, ldc, bias, epi,
+                                                            r, ldr, r_dtype, M, N, K);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ mv_attn_decode
@@ -271,17 +263,14 @@ extern "C" int mv_attn_decode(int dtype, const void* q, int ldq, const void* k_c
   if (ns > 1 && (size_t)ns * R * A * (dh + 2) > ws_floats) return MV_E_WORKSPACE;
   const float scale = 1.0f / sqrtf((float)dh);
   dim3 grid(R * A, ns);
-#define AD_LAUNCH(T_)                                                                                                          \
-  hipLaunchKernelGGL(attn_decode_kernel<T_>, grid, dim3(256), 0, stream, (const T_*)q, ldq, (const T_*)k_cache, (const T_*)v_cache, \
-                     ldkv, slots, ld_slots, slot_row, nk, (T_*)ctx, ldo, ws, A, dh, ns, scale);                                 \
-  MV_CHECK_LAUNCH();                                                                                                          \
-  if (ns > 1) hipLaunchKernelGGL(attn_decode_merge<T_>, dim3(R * A), dim3(128), 0, stream, (const float*)ws, (T_*)ctx, ldo, A, dh, ns);
-  if (dtype == MV_F32) { AD_LAUNCH(float) }
-  else if (dtype == MV_BF16) { AD_LAUNCH(bf16_t) }
-  else { AD_LAUNCH(f16_t) }
-#undef AD_LAUNCH
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    hipLaunchKernelGGL(attn_decode_kernel<T>, grid, dim3(256), 0, stream, (const T*)q, ldq, (const T*)k_cache, (const T*)v_cache, ldkv, slots, ld_slots,
+                       slot_row, nk, (T*)ctx, ldo, ws, A, dh, ns, scale);
+    MV_CHECK_LAUNCH();
+    if (ns > 1) hipLaunchKernelGGL(attn_decode_merge<T>, dim3(R * A), dim3(128), 0, stream, (const float*)ws, (T*)ctx, ldo, A, dh, ns);
+    return (int)hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ mv_logprob_topk
@@ -414,18 +403,12 @@ extern "C" int mv_embed_rows(int dtype, const int64_t* ids, const int64_t* pos, 
     return MV_E_ARG;
   if (ldo < H || H > 8192) return MV_E_SHAPE;
   const size_t lds = (size_t)H * sizeof(float);
-  if (dtype == MV_F32)
-    hipLaunchKernelGGL(embed_rows_kernel<float>, dim3(R), dim3(256), lds, stream, ids, pos, seg, (const float*)E, (const float*)P,
-                       (const float*)Ty, gamma, beta, (float*)out, ldo, H, V, maxpos, ntype, eps);
-  else if (dtype == MV_BF16)
-    hipLaunchKernelGGL(embed_rows_kernel<bf16_t>, dim3(R), dim3(256), lds, stream, ids, pos, seg, (const bf16_t*)E, (const bf16_t*)P,
-                       (const bf16_t*)Ty, gamma, beta, (bf16_t*)out, ldo, H, V, maxpos, ntype, eps);
-  else if (dtype == MV_F16)
-    hipLaunchKernelGGL(embed_rows_kernel<f16_t>, dim3(R), dim3(256), lds, stream, ids, pos, seg, (const f16_t*)E, (const f16_t*)P,
-                       (const f16_t*)Ty, gamma, beta, (f16_t*)out, ldo, H, V, maxpos, ntype, eps);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    hipLaunchKernelGGL(embed_rows_kernel<T>, dim3(R), dim3(256), lds, stream, ids, pos, seg, (const T*)E, (const T*)P, (const T*)Ty, gamma, beta,
+                       (T*)out, ldo, H, V, maxpos, ntype, eps);
+    return (int)hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ mv_ngram_ban

@@ -8,7 +8,7 @@
 //   mv_lm_loss_bwd     one block per row: g * S / denominator * sum over the row's kept entries of w (Q softmax - q)
 //
 // Rows are walked with 16-byte loads when the leading dimension and the base allow it (the MLM head's padded [U, Vp] buffers do).
-#include "mv_common.h"
+#include "mv_dispatch.h"
 
 namespace {
 
@@ -297,12 +297,13 @@ extern "C" int mv_lm_loss_bwd(const float* logits, int ld, int U, int V, const i
   const uintptr_t dal = (uintptr_t)(4 * mv_dtype_size(d_dtype) - 1);
   const bool vec = (ld & 3) == 0 && (ldd & 3) == 0 && (((uintptr_t)logits) & 15) == 0 && (((uintptr_t)dlogits) & dal) == 0;
   const dim3 grid(U), block(256);
-#define LM_BWD(TD, VEC_) hipLaunchKernelGGL((lm_bwd_kernel<TD, VEC_>), grid, block, 0, stream, logits, ld, V, row_ptr, labels, weights, sample, \
-                                            (float)k.conf, k.sval, k.qsum, k.smooth, row_stat, keep, inv_denom, grad_dev, loss_scale_dev, (TD*)dlogits, ldd)
-  if (d_dtype == MV_F32) { if (vec) LM_BWD(float, true); else LM_BWD(float, false); }
-  else if (d_dtype == MV_BF16) { if (vec) LM_BWD(bf16_t, true); else LM_BWD(bf16_t, false); }
-  else { if (vec) LM_BWD(f16_t, true); else LM_BWD(f16_t, false); }
-#undef LM_BWD
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(d_dtype, [&](auto t) -> int {
+    typedef MV_T(t) TD;
+    auto launch = [&](auto kernel) -> int {
+      hipLaunchKernelGGL(kernel, grid, block, 0, stream, logits, ld, V, row_ptr, labels, weights, sample, (float)k.conf, k.sval, k.qsum, k.smooth,
+                         row_stat, keep, inv_denom, grad_dev, loss_scale_dev, (TD*)dlogits, ldd);
+      return (int)hipGetLastError();
+    };
+    return vec ? launch(lm_bwd_kernel<TD, true>) : launch(lm_bwd_kernel<TD, false>);
+  });
 }

@@ -10,7 +10,7 @@
 //                          ceil(count / MV_OPTIM_CHUNK) consecutive chunks starting at first_chunk
 // Tensor sizes span 2 elements to 23 M, so a block works on one equal-sized chunk rather than on one tensor.  Offsets are multiples
 // of 64 elements (engine._align), so a chunk never holds elements of two tensors and every 16-byte access is aligned.
-#include "mv_common.h"
+#include "mv_dispatch.h"
 
 #define MV_LS_SKIP 3          // device state of the dynamic loss scale (mv_rowops.hip): [3] skip flag, [4] optimizer steps applied
 #define MV_LS_T 4
@@ -212,18 +212,16 @@ __global__ __launch_bounds__(64) void bce_ml_kernel(const float* __restrict__ lo
 extern "C" int mv_bce_multilabel(const float* logits, int ld, const float* target, const float* pos_weight, int R, int C, float* loss,
                                  void* dgrad, int d_dtype, int ldd, const float* grad_scale_dev, float grad_scale_host,
                                  const float* loss_scale_dev, float* probs, float* counters, void* stream_) {
+  typedef mv_types<float, bf16_t, f16_t> Accept;      // of dgrad; without dgrad, d_dtype is not looked at (the float instantiation runs)
   hipStream_t stream = (hipStream_t)stream_;
   if (!logits || R <= 0 || C <= 0 || ld < C) return MV_E_ARG;
   if ((loss || dgrad || counters) && !target) return MV_E_ARG;
   if (dgrad && ldd < C) return MV_E_SHAPE;
   const dim3 grid(R), block(64);
-#define BCE_ML_LAUNCH(TD) hipLaunchKernelGGL((bce_ml_kernel<TD>), grid, block, 0, stream, logits, ld, target, pos_weight, C, loss, \
-                                             (TD*)dgrad, ldd, grad_scale_dev, grad_scale_host, loss_scale_dev, probs, counters)
-  if (!dgrad || d_dtype == MV_F32) BCE_ML_LAUNCH(float);
-  else if (d_dtype == MV_BF16) BCE_ML_LAUNCH(bf16_t);
-  else if (d_dtype == MV_F16) BCE_ML_LAUNCH(f16_t);
-  else return MV_E_DTYPE;
-#undef BCE_ML_LAUNCH
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dgrad ? d_dtype : MV_F32, Accept{}, [&](auto t) -> int {
+    typedef MV_T(t) TD;
+    hipLaunchKernelGGL((bce_ml_kernel<TD>), grid, block, 0, stream, logits, ld, target, pos_weight, C, loss, (TD*)dgrad, ldd, grad_scale_dev,
+                       grad_scale_host, loss_scale_dev, probs, counters);
+    return (int)hipGetLastError();
+  });
 }

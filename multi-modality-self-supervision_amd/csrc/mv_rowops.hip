@@ -4,17 +4,9 @@
 // All of them are one-wave-per-row (64 lanes x 4-element vectors) streaming kernels: the
 // roofline that bounds them is HBM bandwidth, so every operand is read once, 8/16 bytes per
 // lane, and every reduction stays in registers / DPP shuffles.
-#include "mv_common.h"
+#include "mv_dispatch.h"
 
-// compile-time number of 256-column chunks per row (keeps the per-row register arrays out of scratch)
-#define NC_DISPATCH(H_, CALL)                                  \
-  do {                                                         \
-    if ((H_) <= 256) { CALL(1); }                              \
-    else if ((H_) <= 768) { CALL(3); }                         \
-    else if ((H_) <= 1024) { CALL(4); }                        \
-    else { CALL(8); }                                          \
-  } while (0)
-#define MV_MAX_H 2048
+#define MV_MAX_H 2048      // mv_with_row_chunks: at most 8 chunks of 256 columns, held in registers (no scratch)
 
 // =========================================================================================
 // LayerNorm
@@ -258,26 +250,29 @@ __global__ __launch_bounds__(64 * WPB) void ln_bwd_pf_kernel(const TD* __restric
 
 extern "C" int mv_layernorm_fwd(int dtype, const void* x, int x_dtype, const float* gamma, const float* beta, void* y, void* y_bf16,
                                 float* mean, float* rstd, int M, int H, float eps, void* stream_) {
+  // (dtype of y, x_dtype): x in y's encoding or in f32
+  typedef mv_pairs<mv_pair<float, float>, mv_pair<bf16_t, float>, mv_pair<bf16_t, bf16_t>, mv_pair<f16_t, float>, mv_pair<f16_t, f16_t>> Accept;
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !gamma || !beta || !y || !mean || !rstd || M <= 0 || H <= 0) return MV_E_ARG;
   if ((H & 3) || H > MV_MAX_H) return MV_E_SHAPE;
   if (y_bf16 && dtype != MV_F16) return MV_E_DTYPE;      // the second output is the bf16 copy of an f16 forward activation
   dim3 grid((M + 3) / 4), block(256);
-#define LNF(NC_) hipLaunchKernelGGL((ln_fwd_kernel<TX_, TY_, NC_>), grid, block, 0, stream, (const TX_*)x, gamma, beta, (TY_*)y, mean, rstd, M, H, eps, (bf16_t*)y_bf16)
-  if (dtype == MV_F32 && x_dtype == MV_F32) { typedef float TX_; typedef float TY_; NC_DISPATCH(H, LNF); }
-  else if (dtype == MV_BF16 && x_dtype == MV_F32) { typedef float TX_; typedef bf16_t TY_; NC_DISPATCH(H, LNF); }
-  else if (dtype == MV_BF16 && x_dtype == MV_BF16) { typedef bf16_t TX_; typedef bf16_t TY_; NC_DISPATCH(H, LNF); }
-  else if (dtype == MV_F16 && x_dtype == MV_F32) { typedef float TX_; typedef f16_t TY_; NC_DISPATCH(H, LNF); }
-  else if (dtype == MV_F16 && x_dtype == MV_F16) { typedef f16_t TX_; typedef f16_t TY_; NC_DISPATCH(H, LNF); }
-  else return MV_E_DTYPE;
-#undef LNF
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_types(dtype, x_dtype, Accept{}, [&](auto ty, auto tx) {
+    typedef MV_T(ty) TY;
+    typedef MV_T(tx) TX;
+    return mv_with_row_chunks(H, [&](auto nc) -> int {
+      hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, nc()>), grid, block, 0, stream, (const TX*)x, gamma, beta, (TY*)y, mean, rstd, M, H, eps, (bf16_t*)y_bf16);
+      return (int)hipGetLastError();
+    });
+  });
 }
 
 extern "C" int mv_layernorm_bwd(int dtype, const void* dy, const void* x, int x_dtype, const float* mean, const float* rstd,
                                 const float* gamma, void* dx, float* dgamma, float* dbeta, float* colsum, int M, int H,
                                 void* dx_drop, float p_drop, unsigned long long drop_key, const float* grad_unscale_dev, void* stream_) {
+  // (dtype of dy and dx, x_dtype): the forward's pairs, and bf16 gradients against the f16 forward's x
+  typedef mv_pairs<mv_pair<float, float>, mv_pair<bf16_t, float>, mv_pair<bf16_t, bf16_t>, mv_pair<bf16_t, f16_t>, mv_pair<f16_t, float>,
+                   mv_pair<f16_t, f16_t>> Accept;
   hipStream_t stream = (hipStream_t)stream_;
   if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || M <= 0 || H <= 0) return MV_E_ARG;
   if ((H & 3) || H > MV_MAX_H) return MV_E_SHAPE;
@@ -291,27 +286,23 @@ extern "C" int mv_layernorm_bwd(int dtype, const void* dy, const void* x, int x_
   dim3 grid(blocks), block(64 * wpb);
   const DropCfg drop = mv_make_drop(dx_drop ? p_drop : 0.f, drop_key);
   if (dx_drop && drop.thr == 0) dx_drop = nullptr;
-#define LNB_ARGS (const TD_*)dy, (const TX_*)x, mean, rstd, gamma, (TD_*)dx, dgamma, dbeta, colsum, M, H, (TD_*)dx_drop, drop, grad_unscale_dev
-#define LNB(NC_)                                                                                                                  \
-  do {                                                                                                                            \
-    constexpr bool wide_ok__ = (NC_) <= 3 && sizeof(TX_) == 2;                                                                    \
-    if constexpr (wide_ok__) {                                                                                                    \
-      if (var == 3) { hipLaunchKernelGGL((ln_bwd_pf_kernel<TX_, TD_, NC_, 16>), grid, block, 0, stream, LNB_ARGS); break; }       \
-      if (var == 0) { hipLaunchKernelGGL((ln_bwd_pf_kernel<TX_, TD_, NC_, 8>), grid, block, 0, stream, LNB_ARGS); break; }        \
-    }                                                                                                                             \
-    if (var != 1) hipLaunchKernelGGL((ln_bwd_pf_kernel<TX_, TD_, NC_, 4>), grid, block, 0, stream, LNB_ARGS);                \
-    else hipLaunchKernelGGL((ln_bwd_kernel<TX_, TD_, NC_>), grid, block, 0, stream, (const TD_*)dy, (const TX_*)x, mean, rstd, gamma, (TD_*)dx, dgamma, dbeta, colsum, M, H, (TD_*)dx_drop, drop, grad_unscale_dev); \
-  } while (0)
-  if (dtype == MV_F32 && x_dtype == MV_F32) { typedef float TX_; typedef float TD_; NC_DISPATCH(H, LNB); }
-  else if (dtype == MV_BF16 && x_dtype == MV_F32) { typedef float TX_; typedef bf16_t TD_; NC_DISPATCH(H, LNB); }
-  else if (dtype == MV_BF16 && x_dtype == MV_BF16) { typedef bf16_t TX_; typedef bf16_t TD_; NC_DISPATCH(H, LNB); }
-  else if (dtype == MV_BF16 && x_dtype == MV_F16) { typedef f16_t TX_; typedef bf16_t TD_; NC_DISPATCH(H, LNB); }
-  else if (dtype == MV_F16 && x_dtype == MV_F32) { typedef float TX_; typedef f16_t TD_; NC_DISPATCH(H, LNB); }
-  else if (dtype == MV_F16 && x_dtype == MV_F16) { typedef f16_t TX_; typedef f16_t TD_; NC_DISPATCH(H, LNB); }
-  else return MV_E_DTYPE;
-#undef LNB
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_types(dtype, x_dtype, Accept{}, [&](auto td, auto tx) {
+    typedef MV_T(td) TD;
+    typedef MV_T(tx) TX;
+    return mv_with_row_chunks(H, [&](auto nc) {
+      constexpr int NC = nc();
+      auto launch = [&](auto kernel) -> int {
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, (const TD*)dy, (const TX*)x, mean, rstd, gamma, (TD*)dx, dgamma, dbeta, colsum, M, H,
+                           (TD*)dx_drop, drop, grad_unscale_dev);
+        return (int)hipGetLastError();
+      };
+      if constexpr (NC <= 3 && sizeof(TX) == 2) {      // the 8- and 16-wave forms exist for these rows only (see above)
+        if (var == 3) return launch(ln_bwd_pf_kernel<TX, TD, NC, 16>);
+        if (var == 0) return launch(ln_bwd_pf_kernel<TX, TD, NC, 8>);
+      }
+      return var != 1 ? launch(ln_bwd_pf_kernel<TX, TD, NC, 4>) : launch(ln_bwd_kernel<TX, TD, NC>);
+    });
+  });
 }
 
 // =========================================================================================
@@ -521,14 +512,14 @@ extern "C" int mv_embed_fwd(int dtype, const int64_t* cls_tok, const int64_t* tx
   dim3 grid((a.n_rows + 3) / 4), block(256);
   const DropCfg drop = mv_make_drop(p_drop, drop_key), drop_img = mv_make_drop(p_drop_img, drop_key);
   if (x0_bf16 && dtype != MV_F16) return MV_E_DTYPE;
-#define EMF(NC_) hipLaunchKernelGGL((embed_fwd_kernel<T_, NC_>), grid, block, 0, stream, a, (const T_*)imgproj, (const T_*)E, (const T_*)P, (const T_*)Ty, gamma, beta, (T_*)x0, pre, mean, rstd, eps, drop, drop_img, (bf16_t*)x0_bf16)
-  if (dtype == MV_F32) { typedef float T_; NC_DISPATCH(H, EMF); }
-  else if (dtype == MV_BF16) { typedef bf16_t T_; NC_DISPATCH(H, EMF); }
-  else if (dtype == MV_F16) { typedef f16_t T_; NC_DISPATCH(H, EMF); }
-  else return MV_E_DTYPE;
-#undef EMF
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, [&](auto t) {
+    typedef MV_T(t) T;
+    return mv_with_row_chunks(H, [&](auto nc) -> int {
+      hipLaunchKernelGGL((embed_fwd_kernel<T, nc()>), grid, block, 0, stream, a, (const T*)imgproj, (const T*)E, (const T*)P, (const T*)Ty, gamma, beta,
+                         (T*)x0, pre, mean, rstd, eps, drop, drop_img, (bf16_t*)x0_bf16);
+      return (int)hipGetLastError();
+    });
+  });
 }
 
 extern "C" int mv_embed_bwd(int dtype, const void* dx0, const float* pre, const float* mean, const float* rstd, const float* gamma,
@@ -549,14 +540,14 @@ extern "C" int mv_embed_bwd(int dtype, const void* dx0, const float* pre, const 
   if (blocks > 1024) blocks = 1024;
   dim3 grid(blocks), block(256);
   const DropCfg drop = mv_make_drop(p_drop, drop_key), drop_img = mv_make_drop(p_drop_img, drop_key);
-#define EMB(NC_) hipLaunchKernelGGL((embed_bwd_kernel<T_, NC_>), grid, block, 0, stream, a, (const T_*)dx0, pre, mean, rstd, gamma, dE, dP, dTy, dgamma, dbeta, (T_*)dimgproj, pad_token_id, MV_HOT_TOKEN, drop, drop_img, grad_unscale_dev)
-  if (dtype == MV_F32) { typedef float T_; NC_DISPATCH(H, EMB); }
-  else if (dtype == MV_BF16) { typedef bf16_t T_; NC_DISPATCH(H, EMB); }
-  else if (dtype == MV_F16) { typedef f16_t T_; NC_DISPATCH(H, EMB); }
-  else return MV_E_DTYPE;
-#undef EMB
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, [&](auto t) {
+    typedef MV_T(t) T;
+    return mv_with_row_chunks(H, [&](auto nc) -> int {
+      hipLaunchKernelGGL((embed_bwd_kernel<T, nc()>), grid, block, 0, stream, a, (const T*)dx0, pre, mean, rstd, gamma, dE, dP, dTy, dgamma, dbeta,
+                         (T*)dimgproj, pad_token_id, MV_HOT_TOKEN, drop, drop_img, grad_unscale_dev);
+      return (int)hipGetLastError();
+    });
+  });
 }
 
 // =========================================================================================
@@ -722,6 +713,9 @@ __global__ __launch_bounds__(NT) void ce_vec_kernel(const TL* __restrict__ logit
 extern "C" int mv_ce_fwd_bwd(const void* logits, int l_dtype, int ld, const int32_t* labels, int R, int V, float* out, void* dlogits,
                              int d_dtype, int ldd, const float* grad_scale_dev, float grad_scale_host, const float* loss_scale_dev,
                              void* stream_) {
+  // (l_dtype, d_dtype): the gradient in the logits' encoding or in f32; from f32 logits in any encoding
+  typedef mv_pairs<mv_pair<float, float>, mv_pair<float, f16_t>, mv_pair<float, bf16_t>, mv_pair<bf16_t, bf16_t>, mv_pair<bf16_t, float>,
+                   mv_pair<f16_t, f16_t>, mv_pair<f16_t, float>> Accept;
   hipStream_t stream = (hipStream_t)stream_;
   if (!logits || !labels || !out || R <= 0 || V <= 0 || ld < V) return MV_E_ARG;
   if (V > 256 * CE_MAXPER) return MV_E_SHAPE;
@@ -729,39 +723,17 @@ extern "C" int mv_ce_fwd_bwd(const void* logits, int l_dtype, int ld, const int3
   dim3 grid(R), block(256);
   const bool vec_ok = ((ld & 3) == 0) && (!dlogits || (ldd & 3) == 0) && ((((uintptr_t)logits) & 15) == 0) &&
                       (!dlogits || (((uintptr_t)dlogits) & 15) == 0) && V > 2048 && ldd <= 1024 * 32 && V <= 1024 * 32;
-  if (vec_ok) {
-    // 1024-thread blocks (32 logits per thread in registers, two blocks per CU) walking rows: more than twice the waves in flight of the
-    // 256-thread form of rounds 1-2 (128 logits per thread, three blocks per CU; 373 -> 179 us alone), one set of result atomics per block
-    const dim3 vgrid(R < 512 ? R : 512), vblock(1024);
-#define CEV_LAUNCH(TL, TD) hipLaunchKernelGGL((ce_vec_kernel<TL, TD, 8, 1024>), vgrid, vblock, 0, stream, (const TL*)logits, ld, labels, R, V, out, (TD*)dlogits, ldd, grad_scale_dev, grad_scale_host, loss_scale_dev)
-    if (l_dtype == MV_F32 && d_dtype == MV_F32) CEV_LAUNCH(float, float);
-    else if (l_dtype == MV_F32 && d_dtype == MV_F16) CEV_LAUNCH(float, f16_t);
-    else if (l_dtype == MV_F32 && d_dtype == MV_BF16) CEV_LAUNCH(float, bf16_t);
-    else if (l_dtype == MV_BF16 && d_dtype == MV_BF16) CEV_LAUNCH(bf16_t, bf16_t);
-    else if (l_dtype == MV_BF16 && d_dtype == MV_F32) CEV_LAUNCH(bf16_t, float);
-    else if (l_dtype == MV_F16 && d_dtype == MV_F16) CEV_LAUNCH(f16_t, f16_t);
-    else if (l_dtype == MV_F16 && d_dtype == MV_F32) CEV_LAUNCH(f16_t, float);
-    else return MV_E_DTYPE;
-#undef CEV_LAUNCH
-    MV_CHECK_LAUNCH();
-    return MV_OK;
-  }
-#define CE_LAUNCH(TL, TD)                                                                                              \
-  do {                                                                                                                 \
-    if (V <= 256 * 8) hipLaunchKernelGGL((ce_kernel<TL, TD, 8>), grid, block, 0, stream, (const TL*)logits, ld, labels, R, V, out, (TD*)dlogits, ldd, grad_scale_dev, grad_scale_host, loss_scale_dev); \
-    else hipLaunchKernelGGL((ce_kernel<TL, TD, CE_MAXPER>), grid, block, 0, stream, (const TL*)logits, ld, labels, R, V, out, (TD*)dlogits, ldd, grad_scale_dev, grad_scale_host, loss_scale_dev); \
-  } while (0)
-  if (l_dtype == MV_F32 && d_dtype == MV_F32) CE_LAUNCH(float, float);
-  else if (l_dtype == MV_F32 && d_dtype == MV_F16) CE_LAUNCH(float, f16_t);
-  else if (l_dtype == MV_F32 && d_dtype == MV_BF16) CE_LAUNCH(float, bf16_t);
-  else if (l_dtype == MV_BF16 && d_dtype == MV_BF16) CE_LAUNCH(bf16_t, bf16_t);
-  else if (l_dtype == MV_BF16 && d_dtype == MV_F32) CE_LAUNCH(bf16_t, float);
-  else if (l_dtype == MV_F16 && d_dtype == MV_F16) CE_LAUNCH(f16_t, f16_t);
-  else if (l_dtype == MV_F16 && d_dtype == MV_F32) CE_LAUNCH(f16_t, float);
-  else return MV_E_DTYPE;
-#undef CE_LAUNCH
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  // vec_ok: 1024-thread blocks (32 logits per thread in registers, two blocks per CU) walking rows: more than twice the waves in flight of the
+  // 256-thread form of rounds 1-2 (128 logits per thread, three blocks per CU; 373 -> 179 us alone), one set of result atomics per block
+  const dim3 vgrid(R < 512 ? R : 512), vblock(1024);
+  return mv_with_types(l_dtype, d_dtype, Accept{}, [&](auto tl, auto td) -> int {
+    typedef MV_T(tl) TL;
+    typedef MV_T(td) TD;
+    if (vec_ok) hipLaunchKernelGGL((ce_vec_kernel<TL, TD, 8, 1024>), vgrid, vblock, 0, stream, (const TL*)logits, ld, labels, R, V, out, (TD*)dlogits, ldd, grad_scale_dev, grad_scale_host, loss_scale_dev);
+    else if (V <= 256 * 8) hipLaunchKernelGGL((ce_kernel<TL, TD, 8>), grid, block, 0, stream, (const TL*)logits, ld, labels, R, V, out, (TD*)dlogits, ldd, grad_scale_dev, grad_scale_host, loss_scale_dev);
+    else hipLaunchKernelGGL((ce_kernel<TL, TD, CE_MAXPER>), grid, block, 0, stream, (const TL*)logits, ld, labels, R, V, out, (TD*)dlogits, ldd, grad_scale_dev, grad_scale_host, loss_scale_dev);
+    return (int)hipGetLastError();
+  });
 }
 
 // =========================================================================================
@@ -802,12 +774,11 @@ extern "C" int mv_gather_rows(int dtype, const void* src, int lds_, const int32_
   if (!src || !rows || !dst || R <= 0 || H <= 0) return MV_E_ARG;
   if ((H & 3) || (lds_ & 3) || (ldd & 3)) return MV_E_SHAPE;
   dim3 grid((R + 3) / 4), block(256);
-  if (dtype == MV_F32) hipLaunchKernelGGL(gather_rows_kernel<float>, grid, block, 0, stream, (const float*)src, lds_, rows, R, H, (float*)dst, ldd);
-  else if (dtype == MV_BF16) hipLaunchKernelGGL(gather_rows_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)src, lds_, rows, R, H, (bf16_t*)dst, ldd);
-  else if (dtype == MV_F16) hipLaunchKernelGGL(gather_rows_kernel<f16_t>, grid, block, 0, stream, (const f16_t*)src, lds_, rows, R, H, (f16_t*)dst, ldd);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    hipLaunchKernelGGL(gather_rows_kernel<T>, grid, block, 0, stream, (const T*)src, lds_, rows, R, H, (T*)dst, ldd);
+    return (int)hipGetLastError();
+  });
 }
 extern "C" int mv_scatter_rows(int dtype, const void* src, int lds_, const int32_t* rows, int R, int H, void* dst, int ldd,
                                int accumulate, void* stream_) {
@@ -815,12 +786,11 @@ extern "C" int mv_scatter_rows(int dtype, const void* src, int lds_, const int32
   if (!src || !rows || !dst || R <= 0 || H <= 0) return MV_E_ARG;
   if ((H & 3) || (lds_ & 3) || (ldd & 3)) return MV_E_SHAPE;
   dim3 grid((R + 3) / 4), block(256);
-  if (dtype == MV_F32) hipLaunchKernelGGL(scatter_rows_kernel<float>, grid, block, 0, stream, (const float*)src, lds_, rows, R, H, (float*)dst, ldd, accumulate);
-  else if (dtype == MV_BF16) hipLaunchKernelGGL(scatter_rows_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)src, lds_, rows, R, H, (bf16_t*)dst, ldd, accumulate);
-  else if (dtype == MV_F16) hipLaunchKernelGGL(scatter_rows_kernel<f16_t>, grid, block, 0, stream, (const f16_t*)src, lds_, rows, R, H, (f16_t*)dst, ldd, accumulate);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    hipLaunchKernelGGL(scatter_rows_kernel<T>, grid, block, 0, stream, (const T*)src, lds_, rows, R, H, (T*)dst, ldd, accumulate);
+    return (int)hipGetLastError();
+  });
 }
 
 // out[n] += sum_m x[m,n].  A block owns a strip of 128 (f32) / 256 (bf16) columns: 32 lanes x one 16-byte vector
@@ -876,6 +846,7 @@ __global__ void zero_f32_kernel(float* p, size_t n) {
 
 extern "C" int mv_colsum(int dtype, const void* x, int ldx, int M, int N, float* out, int accumulate, const float* grad_unscale_dev,
                          void* stream_) {
+  typedef mv_types<float, bf16_t, f16_t> Accept;      // refused only after the zero-fill below has been enqueued
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !out || M <= 0 || N <= 0 || ldx < N) return MV_E_ARG;
   if (!accumulate) {
@@ -889,12 +860,11 @@ extern "C" int mv_colsum(int dtype, const void* x, int ldx, int M, int N, float*
   if (ysplit > want) ysplit = want;
   if (ysplit < 1) ysplit = 1;
   dim3 grid(xb, ysplit), block(256);
-  if (dtype == MV_F32) hipLaunchKernelGGL(colsum_kernel<float>, grid, block, 0, stream, (const float*)x, ldx, M, N, out, grad_unscale_dev);
-  else if (dtype == MV_BF16) hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)x, ldx, M, N, out, grad_unscale_dev);
-  else if (dtype == MV_F16) hipLaunchKernelGGL(colsum_kernel<f16_t>, grid, block, 0, stream, (const f16_t*)x, ldx, M, N, out, grad_unscale_dev);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, Accept{}, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    hipLaunchKernelGGL(colsum_kernel<T>, grid, block, 0, stream, (const T*)x, ldx, M, N, out, grad_unscale_dev);
+    return (int)hipGetLastError();
+  });
 }
 
 // out[n] += [*gscale] * sum_p part[p, n]: folds the per-block partial column sums that the attention backward (and the dz GEMM's
@@ -961,12 +931,11 @@ extern "C" int mv_add(int dtype, const void* a, const void* b, void* c, size_t n
   const size_t n4 = n / 4;
   int blocks = (int)((n4 + 255) / 256);
   if (blocks > 2048) blocks = 2048;
-  if (dtype == MV_F32) hipLaunchKernelGGL(add_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float*)a, (const float*)b, (float*)c, n4);
-  else if (dtype == MV_BF16) hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)c, n4);
-  else if (dtype == MV_F16) hipLaunchKernelGGL(add_kernel<f16_t>, dim3(blocks), dim3(256), 0, stream, (const f16_t*)a, (const f16_t*)b, (f16_t*)c, n4);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    hipLaunchKernelGGL(add_kernel<T>, dim3(blocks), dim3(256), 0, stream, (const T*)a, (const T*)b, (T*)c, n4);
+    return (int)hipGetLastError();
+  });
 }
 
 // out = dy * gelu'(z)   (mode 0)   |   out = dy * (1 - y*y)   (mode 1: tanh backward, z holds y)   |   out = dy * (y > 0)   (mode 2:
@@ -988,12 +957,11 @@ extern "C" int mv_dact(int dtype, int mode, const void* dy, const void* z, void*
   const size_t n4 = n / 4;
   int blocks = (int)((n4 + 255) / 256);
   if (blocks > 2048) blocks = 2048;
-  if (dtype == MV_F32) hipLaunchKernelGGL(dact_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float*)dy, (const float*)z, (float*)out, n4, mode);
-  else if (dtype == MV_BF16) hipLaunchKernelGGL(dact_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)dy, (const bf16_t*)z, (bf16_t*)out, n4, mode);
-  else if (dtype == MV_F16) hipLaunchKernelGGL(dact_kernel<f16_t>, dim3(blocks), dim3(256), 0, stream, (const f16_t*)dy, (const f16_t*)z, (f16_t*)out, n4, mode);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    hipLaunchKernelGGL(dact_kernel<T>, dim3(blocks), dim3(256), 0, stream, (const T*)dy, (const T*)z, (T*)out, n4, mode);
+    return (int)hipGetLastError();
+  });
 }
 
 // 2-D cast with leading dimensions; columns cols..ldd-1 of dst are zero-filled
@@ -1007,6 +975,9 @@ __global__ void cast2d_kernel(const TS* __restrict__ s, long long lds_, TDs* __r
 }
 extern "C" int mv_cast2d(const void* src, int src_dtype, long long lds_, void* dst, int dst_dtype, long long ldd, int rows, int cols,
                          void* stream_) {
+  // (src_dtype, dst_dtype): to and from f32, and copies; unlike mv_cast, no f16 <-> bf16
+  typedef mv_pairs<mv_pair<float, bf16_t>, mv_pair<bf16_t, float>, mv_pair<float, float>, mv_pair<bf16_t, bf16_t>, mv_pair<float, f16_t>,
+                   mv_pair<f16_t, float>, mv_pair<f16_t, f16_t>> Accept;
   hipStream_t stream = (hipStream_t)stream_;
   if (!src || !dst || rows <= 0 || cols <= 0 || lds_ < cols || ldd < cols) return MV_E_ARG;
   if (rows > 65535 * 16) return MV_E_SHAPE;
@@ -1017,15 +988,13 @@ extern "C" int mv_cast2d(const void* src, int src_dtype, long long lds_, void* d
     dim3 grid(bx, nr), block(256);
     const char* sp = (const char*)src + (size_t)r0 * lds_ * mv_dtype_size(src_dtype);
     char* dp = (char*)dst + (size_t)r0 * ldd * mv_dtype_size(dst_dtype);
-    if (src_dtype == MV_F32 && dst_dtype == MV_BF16) hipLaunchKernelGGL((cast2d_kernel<float, bf16_t>), grid, block, 0, stream, (const float*)sp, lds_, (bf16_t*)dp, ldd, nr, cols);
-    else if (src_dtype == MV_BF16 && dst_dtype == MV_F32) hipLaunchKernelGGL((cast2d_kernel<bf16_t, float>), grid, block, 0, stream, (const bf16_t*)sp, lds_, (float*)dp, ldd, nr, cols);
-    else if (src_dtype == MV_F32 && dst_dtype == MV_F32) hipLaunchKernelGGL((cast2d_kernel<float, float>), grid, block, 0, stream, (const float*)sp, lds_, (float*)dp, ldd, nr, cols);
-    else if (src_dtype == MV_BF16 && dst_dtype == MV_BF16) hipLaunchKernelGGL((cast2d_kernel<bf16_t, bf16_t>), grid, block, 0, stream, (const bf16_t*)sp, lds_, (bf16_t*)dp, ldd, nr, cols);
-    else if (src_dtype == MV_F32 && dst_dtype == MV_F16) hipLaunchKernelGGL((cast2d_kernel<float, f16_t>), grid, block, 0, stream, (const float*)sp, lds_, (f16_t*)dp, ldd, nr, cols);
-    else if (src_dtype == MV_F16 && dst_dtype == MV_F32) hipLaunchKernelGGL((cast2d_kernel<f16_t, float>), grid, block, 0, stream, (const f16_t*)sp, lds_, (float*)dp, ldd, nr, cols);
-    else if (src_dtype == MV_F16 && dst_dtype == MV_F16) hipLaunchKernelGGL((cast2d_kernel<f16_t, f16_t>), grid, block, 0, stream, (const f16_t*)sp, lds_, (f16_t*)dp, ldd, nr, cols);
-    else return MV_E_DTYPE;
-    MV_CHECK_LAUNCH();
+    const int rc = mv_with_types(src_dtype, dst_dtype, Accept{}, [&](auto ts, auto td) -> int {
+      typedef MV_T(ts) TS;
+      typedef MV_T(td) TD;
+      hipLaunchKernelGGL((cast2d_kernel<TS, TD>), grid, block, 0, stream, (const TS*)sp, lds_, (TD*)dp, ldd, nr, cols);
+      return (int)hipGetLastError();
+    });
+    if (rc) return rc;
   }
   return MV_OK;
 }
@@ -1051,15 +1020,16 @@ __global__ __launch_bounds__(256) void transpose_kernel(const T* __restrict__ sr
   }
 }
 extern "C" int mv_transpose(int dtype, const void* src, long long lds_, void* dst, long long ldd, int rows, int cols, void* stream_) {
+  typedef mv_types<float, bf16_t, f16_t> Accept;      // f16 runs the bf16 instantiation: 2-byte elements move as bits (mv_bits_t)
   hipStream_t stream = (hipStream_t)stream_;
   if (!src || !dst || rows <= 0 || cols <= 0 || lds_ < cols || ldd < rows) return MV_E_ARG;
   dim3 grid((cols + 63) / 64, (rows + 63) / 64), block(256);
   if (grid.y > 65535) return MV_E_SHAPE;
-  if (dtype == MV_BF16 || dtype == MV_F16) hipLaunchKernelGGL(transpose_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)src, lds_, (bf16_t*)dst, ldd, rows, cols);   // 2-byte elements move as bits
-  else if (dtype == MV_F32) hipLaunchKernelGGL(transpose_kernel<float>, grid, block, 0, stream, (const float*)src, lds_, (float*)dst, ldd, rows, cols);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, Accept{}, [&](auto t) -> int {
+    typedef mv_bits_t<MV_T(t)> T;
+    hipLaunchKernelGGL(transpose_kernel<T>, grid, block, 0, stream, (const T*)src, lds_, (T*)dst, ldd, rows, cols);
+    return (int)hipGetLastError();
+  });
 }
 
 template <typename TS, typename TDs>
@@ -1070,23 +1040,20 @@ __global__ void cast_kernel(const TS* __restrict__ s, TDs* __restrict__ d, size_
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) stf<TDs>(d + n4 * 4 + threadIdx.x, ldf<TS>(s + n4 * 4 + threadIdx.x));
 }
 extern "C" int mv_cast(const void* src, int src_dtype, void* dst, int dst_dtype, size_t n, void* stream_) {
+  // (src_dtype, dst_dtype): all nine
+  typedef mv_pairs<mv_pair<float, float>, mv_pair<float, bf16_t>, mv_pair<float, f16_t>, mv_pair<bf16_t, float>, mv_pair<bf16_t, bf16_t>,
+                   mv_pair<bf16_t, f16_t>, mv_pair<f16_t, float>, mv_pair<f16_t, bf16_t>, mv_pair<f16_t, f16_t>> Accept;
   hipStream_t stream = (hipStream_t)stream_;
   if (!src || !dst || n == 0) return MV_E_ARG;
   int blocks = (int)((n / 4 + 255) / 256);
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  if (src_dtype == MV_F32 && dst_dtype == MV_BF16) hipLaunchKernelGGL((cast_kernel<float, bf16_t>), dim3(blocks), dim3(256), 0, stream, (const float*)src, (bf16_t*)dst, n);
-  else if (src_dtype == MV_BF16 && dst_dtype == MV_F32) hipLaunchKernelGGL((cast_kernel<bf16_t, float>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)src, (float*)dst, n);
-  else if (src_dtype == MV_F32 && dst_dtype == MV_F32) hipLaunchKernelGGL((cast_kernel<float, float>), dim3(blocks), dim3(256), 0, stream, (const float*)src, (float*)dst, n);
-  else if (src_dtype == MV_BF16 && dst_dtype == MV_BF16) hipLaunchKernelGGL((cast_kernel<bf16_t, bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)src, (bf16_t*)dst, n);
-  else if (src_dtype == MV_F32 && dst_dtype == MV_F16) hipLaunchKernelGGL((cast_kernel<float, f16_t>), dim3(blocks), dim3(256), 0, stream, (const float*)src, (f16_t*)dst, n);
-  else if (src_dtype == MV_F16 && dst_dtype == MV_F32) hipLaunchKernelGGL((cast_kernel<f16_t, float>), dim3(blocks), dim3(256), 0, stream, (const f16_t*)src, (float*)dst, n);
-  else if (src_dtype == MV_F16 && dst_dtype == MV_BF16) hipLaunchKernelGGL((cast_kernel<f16_t, bf16_t>), dim3(blocks), dim3(256), 0, stream, (const f16_t*)src, (bf16_t*)dst, n);
-  else if (src_dtype == MV_BF16 && dst_dtype == MV_F16) hipLaunchKernelGGL((cast_kernel<bf16_t, f16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)src, (f16_t*)dst, n);
-  else if (src_dtype == MV_F16 && dst_dtype == MV_F16) hipLaunchKernelGGL((cast_kernel<f16_t, f16_t>), dim3(blocks), dim3(256), 0, stream, (const f16_t*)src, (f16_t*)dst, n);
-  else return MV_E_DTYPE;
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_types(src_dtype, dst_dtype, Accept{}, [&](auto ts, auto td) -> int {
+    typedef MV_T(ts) TS;
+    typedef MV_T(td) TD;
+    hipLaunchKernelGGL((cast_kernel<TS, TD>), dim3(blocks), dim3(256), 0, stream, (const TS*)src, (TD*)dst, n);
+    return (int)hipGetLastError();
+  });
 }
 
 // =========================================================================================

@@ -4,7 +4,7 @@
 //
 //   mv_bce_fwd_bwd  BCEWithLogits over soft targets (sum), its gradient, the training / inference argmax and the VQA score split
 //   mv_rows_mul     out[i] = a[rows_a[i]] * b[rows_b[i]]   (the [CLS] (.) [SEP] inference embedding from the compact hidden state)
-#include "mv_common.h"
+#include "mv_dispatch.h"
 
 // ------------------------------------------------------------------------------------------------ mv_bce_fwd_bwd
 // Block = one row, 256 threads walk its columns (A = 458: two per thread).  Per column: the stable element loss
@@ -75,20 +75,18 @@ __global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ logi
 extern "C" int mv_bce_fwd_bwd(const float* logits, int ld, const float* target, const int32_t* ans_type, int R, int A, float* stats,
                               void* dgrad, int d_dtype, int ldd, const float* grad_scale_dev, float grad_scale_host,
                               const float* loss_scale_dev, int64_t* arg_train, int64_t* arg_infer, void* stream_) {
+  typedef mv_types<float, bf16_t, f16_t> Accept;      // of dgrad; without dgrad, d_dtype is not looked at (the float instantiation runs)
   hipStream_t stream = (hipStream_t)stream_;
   if (!logits || R <= 0 || A <= 0 || ld < A) return MV_E_ARG;
   if ((stats || dgrad) && !target) return MV_E_ARG;
   if (dgrad && ldd < A) return MV_E_SHAPE;
   const dim3 grid(R), block(256);
-#define BCE_LAUNCH(TD) hipLaunchKernelGGL((bce_kernel<TD>), grid, block, 0, stream, logits, ld, target, ans_type, A, stats, (TD*)dgrad, ldd, \
-                                          grad_scale_dev, grad_scale_host, loss_scale_dev, arg_train, arg_infer)
-  if (!dgrad || d_dtype == MV_F32) BCE_LAUNCH(float);
-  else if (d_dtype == MV_BF16) BCE_LAUNCH(bf16_t);
-  else if (d_dtype == MV_F16) BCE_LAUNCH(f16_t);
-  else return MV_E_DTYPE;
-#undef BCE_LAUNCH
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dgrad ? d_dtype : MV_F32, Accept{}, [&](auto t) -> int {
+    typedef MV_T(t) TD;
+    hipLaunchKernelGGL((bce_kernel<TD>), grid, block, 0, stream, logits, ld, target, ans_type, A, stats, (TD*)dgrad, ldd, grad_scale_dev,
+                       grad_scale_host, loss_scale_dev, arg_train, arg_infer);
+    return (int)hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ mv_rows_mul
@@ -117,12 +115,9 @@ extern "C" int mv_rows_mul(int dtype, const void* a, int lda, const int32_t* row
   const uintptr_t al = (uintptr_t)(4 * mv_dtype_size(dtype) - 1);
   if ((((uintptr_t)a) & al) || (((uintptr_t)b) & al) || (((uintptr_t)out) & al)) return MV_E_SHAPE;
   const dim3 grid((R + 3) / 4), block(256);
-  if (dtype == MV_F32)
-    hipLaunchKernelGGL(rows_mul_kernel<float>, grid, block, 0, stream, (const float*)a, lda, rows_a, (const float*)b, ldb, rows_b, R, H, (float*)out, ldo);
-  else if (dtype == MV_BF16)
-    hipLaunchKernelGGL(rows_mul_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)a, lda, rows_a, (const bf16_t*)b, ldb, rows_b, R, H, (bf16_t*)out, ldo);
-  else
-    hipLaunchKernelGGL(rows_mul_kernel<f16_t>, grid, block, 0, stream, (const f16_t*)a, lda, rows_a, (const f16_t*)b, ldb, rows_b, R, H, (f16_t*)out, ldo);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  return mv_with_type(dtype, [&](auto t) -> int {
+    typedef MV_T(t) T;
+    hipLaunchKernelGGL(rows_mul_kernel<T>, grid, block, 0, stream, (const T*)a, lda, rows_a, (const T*)b, ldb, rows_b, R, H, (T*)out, ldo);
+    return (int)hipGetLastError();
+  });
 }

@@ -122,7 +122,7 @@ def test_the_caps_in_the_source_are_the_caps_of_the_predicates():
     assert num(r"grid_for\(size_t n, int per_block = (\d+), int cap = \d+\)") == C.THREADS
     assert num(r"grid_for\(size_t n, int per_block = \d+, int cap = (\d+)\)") == C.GRID_CAP
     launches = re.findall(r"<<<grid_for\([^;]*?\), (\d+), 0, stream>>>", src)
-    assert len(launches) == len(re.findall(r"<<<grid_for\(", src)) == 10 and set(launches) == {str(C.THREADS)}     # 2 nhwc, 3 im2col, 3 bn_act, 2 maxpool
+    assert len(launches) == len(re.findall(r"<<<grid_for\(", src)) == 5 and set(launches) == {str(C.THREADS)}     # 1 nhwc, 2 im2col, 1 bn_act, 1 maxpool: once per entry point and vector width
     assert num(r"int slabs = \(rows \+ (\d+)\) / \d+;") + 1 == C.SLAB_ROWS and num(r"int slabs = \(rows \+ \d+\) / (\d+);") == C.SLAB_ROWS
     assert num(r"if \(slabs > (\d+)\) slabs = \1;") == C.SLAB_CAP
     assert num(r"const int c = blockIdx\.x \* (\d+) \+ cg \* 4;") == C.COLS_PER_BLOCK

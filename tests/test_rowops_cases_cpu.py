@@ -139,7 +139,9 @@ def test_the_caps_in_the_source_are_the_caps_of_the_predicates():
     assert num(src, r"#define CE_MAXPER (\d+)") * 256 == C.CE_MAX_V
     assert "ce_vec_kernel<TL, TD, 8, 1024>" in ce                 # 8 vectors x 1024 threads x 4 columns = CE_VEC_MAX
     assert num(src, r"#define MV_MAX_H (\d+)") == C.LN_MAX_H
-    m = re.search(r"#define NC_DISPATCH.*?\(H_\) <= (\d+)\) \{ CALL\(1\).*?\(H_\) <= (\d+)\) \{ CALL\(3\).*?\(H_\) <= (\d+)\) \{ CALL\(4\).*?CALL\(8\)", src, re.S)
+    disp = open(os.path.join(os.path.dirname(HIP), "mv_dispatch.h")).read()       # the row kernels' chunk count: mv_with_row_chunks
+    m = re.search(r"mv_with_row_chunks\(int H,.*?H <= (\d+)\) return f\(std::integral_constant<int, 1>.*?H <= (\d+)\) return f\(std::integral_constant<int, 3>"
+                  r".*?H <= (\d+)\) return f\(std::integral_constant<int, 4>.*?return f\(std::integral_constant<int, 8>", disp, re.S)
     assert m and tuple(int(x) for x in m.groups()) == C.LN_NC_STEPS
     lnb = _body(src, "mv_layernorm_bwd")
     m = re.search(r"var == 0 \? (\d+) : var == 3 \? (\d+) : (\d+)\);", lnb)
