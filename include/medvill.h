@@ -685,6 +685,45 @@ int mv_pair_assemble(const int64_t* txt_ids, const int32_t* txt_len, int T_items
 int mv_rank_groups(const float* logits, const int32_t* labels, int G, int C, const int32_t* ks, int nk, float* p, int32_t* pos,
                    int32_t* rank, unsigned long long* counters, void* stream);
 
+/* ---- report fine-tuning from a device-resident bank (csrc/mv_report.hip) ---------------------------------------------------
+ * The reference's Preprocess4Seq2seq (Downstream_task/report_generation_and_vqa/sc/data_loader.py:330-419) from banks that live on the
+ * device, and the row plan of CXRBertForReportFinetune (report_finetune.build_plan) without the host.  Additive entry points.
+ *
+ * mv_report_draws: the masking draw's random words.  draws uint32 [B, T+1]: word (i, t) = the counter-based hash keyed by (key, step)
+ *     -- one stream per pair, derived as mv_pair_draws derives it -- at counter i (T+1) + t.  Words t < T are the shuffle keys of text
+ *     index t, word T is the coin.
+ * mv_report_assemble: one launch per batch.  Banks: txt_ids int64 [n_items, T] (each row tokens + [SEP] + [PAD]...), txt_len int32
+ *     [n_items] (counting the [SEP]; clamped to [1, T]), n_pred int32 [n_items], img_feats [n_items, N, F] (dtype), img_pos int64
+ *     [n_items, N].  Per batch: idx int32 [B] (an index outside the bank is clamped into it), family int32 [B] (nullable = 1, the
+ *     seq2seq family), draws uint32 [B, T+1] (nullable; replaces the hash).  For slot i with item d = idx[i], len = txt_len[d] and
+ *     p = min(n_pred[d], max_pred, len): the candidates are the text indices 0 .. len-1 (the last is the [SEP]); the rank of t is the
+ *     number of candidates t' with (word[t'], t') < (word[t], t) -- equal words go to the lower index; coin = the top bit of word T.
+ *     coin set: slots 0 .. p-2 list the indices of ranks 0 .. p-2 and slot p-1 lists index len-1 (so the [SEP] can be listed twice,
+ *     data_loader.py:357-360); else slots 0 .. p-1 list ranks 0 .. p-1.  A slot that lists index t holds masked_pos = N + 2 + t,
+ *     masked_lm_labels = txt_ids[d, t], masked_weights = 1; slots p .. max_pred-1 hold (0, 0, 0).
+ *     Writes input_txt int64 [B, T] (the bank row with 103 = [MASK] at every listed index), segment int64 [B, T] (1 for t < len, else
+ *     0), desc int32 [B, 3] = {family, N+2, N+2+len}, feats [B, N, F] (dtype), pos_out int64 [B, N], masked_pos / masked_lm_labels
+ *     int64 [B, max_pred], masked_weights f32 [B, max_pred].  T <= 1024, max_pred <= 64.
+ * mv_report_plan: the prediction lists -> the distinct consumed rows and the entries in CSR form over them (what mv_lm_loss_* and the
+ *     encoder's consumed-rows last layer take).  pos / labels int64 [B, P], weights f32 [B, P], valid_len int32 [B] (nullable; packed
+ *     rows).  A slot of weight 0 is dropped.  Any other slot is BAD when its weight is negative or not finite, its position is <= 0,
+ *     >= L or >= valid_len[b], or its label lies outside [0, V): it is counted and left out.  The others are the entries.
+ *     rows int32 [U] = the distinct b L + pos, ascending; row_ptr int32 [U+1] (row_ptr[U] = n); labels int32 [n], weights f32 [n],
+ *     sample int32 [n]: grouped by row, in slot order inside a row; counts int32 [4] = {U, n, bad, 0}.  Every output array holds
+ *     B P elements (row_ptr one more); elements past U / n are not written.  work: int32 [3 B] scratch.  Two launches (one wave per
+ *     sample: count, then offsets and write), no atomics: fully defined and bitwise reproducible.  P <= 64, B <= 2048, B L < 2^31.
+ * Null pointers (family, draws, valid_len excepted), non-positive sizes: MV_E_ARG; unknown dtype: MV_E_DTYPE; beyond the limits above
+ * or the 32-bit hash counters (B (T+1) >= 2^30): MV_E_SHAPE.  */
+int mv_report_draws(unsigned long long key, unsigned long long step, int B, int T, uint32_t* draws, void* stream);
+int mv_report_assemble(const int64_t* txt_ids, const int32_t* txt_len, const int32_t* n_pred, int n_items, const void* img_feats,
+                       int dtype, const int64_t* img_pos, const int32_t* idx, const int32_t* family, int B, int N, int T, int F,
+                       int max_pred, unsigned long long key, unsigned long long step, const uint32_t* draws, int64_t* input_txt,
+                       int64_t* segment, int32_t* desc, void* feats, int64_t* pos_out, int64_t* masked_pos, int64_t* masked_lm_labels,
+                       float* masked_weights, void* stream);
+int mv_report_plan(const int64_t* pos, const int64_t* labels, const float* weights, const int32_t* valid_len, int B, int P, int L, int V,
+                   int32_t* work, int32_t* rows, int32_t* row_ptr, int32_t* out_labels, float* out_weights, int32_t* out_sample,
+                   int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

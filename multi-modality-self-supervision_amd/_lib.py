@@ -104,6 +104,10 @@ PROTOTYPES = {
     "mv_pair_negatives": [vp, i32, i32, vp, u64, u64, vp, i32, vp, vp, vp],
     "mv_pair_assemble": [vp, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "mv_rank_groups": [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp],
+    # report fine-tuning from a device-resident bank (csrc/mv_report.hip)
+    "mv_report_draws": [u64, u64, i32, i32, vp, vp],
+    "mv_report_assemble": [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "mv_report_plan": [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
 }
 # include/medvill_debug.h: exported by libmedvill_hip_dbg.so only
 DEBUG_PROTOTYPES = {"mv_debug_set_knob": [i32, i32], "mv_debug_get_knob": [i32]}

@@ -182,6 +182,12 @@ __device__ __forceinline__ float mv_drop1(float v, size_t idx, const DropCfg& d)
   const unsigned h = mv_hash32((unsigned)(idx >> 1), d.k0, d.k1);
   return mv_keep(h, (int)(idx & 1), d.thr) ? v * d.inv_keep : 0.f;
 }
+// the hash keys of the samplers (mv_pair_*, mv_report_*): one stream per (key, step)
+static inline void mv_derive_keys(unsigned long long key, unsigned long long step, unsigned& k0, unsigned& k1) {
+  const unsigned long long kk = key ^ (step * 0x9E3779B97F4A7C15ULL);
+  k0 = (unsigned)(kk & 0xffffffffULL);
+  k1 = (unsigned)(kk >> 32);
+}
 static inline DropCfg mv_make_drop(float p, unsigned long long key) {
   DropCfg d;
   int thr = (int)(p * 65536.0f + 0.5f);
@@ -226,3 +232,23 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 static inline int mv_dtype_size(int dt) { return dt == MV_F32 ? 4 : 2; }   // MV_BF16 and MV_F16 are both 2 bytes
+
+// One block's share of a row copy (the bank gathers of mv_pair_assemble / mv_report_assemble): bytes [lo, min(n, lo + chunk)) of s -> d
+// by the block's nt threads.  vec16: n, chunk and both bases are multiples of 16 -> 16 bytes per lane; else 2-byte units (every
+// encoding's size divides into them).
+__device__ __forceinline__ void mv_copy_chunk(const unsigned char* __restrict__ s, unsigned char* __restrict__ d, size_t n, size_t lo,
+                                              size_t chunk, int vec16, int nt) {
+  if (lo >= n) return;
+  const size_t hi = min(n, lo + chunk);
+  if (vec16) {
+    const uint4* s4 = (const uint4*)(s + lo);
+    uint4* d4 = (uint4*)(d + lo);
+    const size_t n4 = (hi - lo) >> 4;
+    for (size_t i = threadIdx.x; i < n4; i += nt) d4[i] = s4[i];
+  } else {
+    const uint16_t* s2 = (const uint16_t*)(s + lo);
+    uint16_t* d2 = (uint16_t*)(d + lo);
+    const size_t n2 = (hi - lo) >> 1;
+    for (size_t i = threadIdx.x; i < n2; i += nt) d2[i] = s2[i];
+  }
+}

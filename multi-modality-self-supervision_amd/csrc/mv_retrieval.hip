@@ -94,22 +94,8 @@ __global__ __launch_bounds__(NT) void pair_assemble_kernel(const int64_t* __rest
       desc[3 * r + 2] = N + 2 + len;
     }
   }
-  const size_t lo = (size_t)blockIdx.y * chunk_bytes;
-  if (lo >= row_bytes) return;
-  const size_t hi = min(row_bytes, lo + chunk_bytes);
-  const unsigned char* s = img + (size_t)im * row_bytes;
-  unsigned char* d = feats + (size_t)r * row_bytes;
-  if (vec16) {
-    const uint4* s4 = (const uint4*)(s + lo);
-    uint4* d4 = (uint4*)(d + lo);
-    const size_t n4 = (hi - lo) >> 4;
-    for (size_t i = threadIdx.x; i < n4; i += NT) d4[i] = s4[i];
-  } else {                                                        // 2-byte units: every encoding's size divides into them
-    const uint16_t* s2 = (const uint16_t*)(s + lo);
-    uint16_t* d2 = (uint16_t*)(d + lo);
-    const size_t n2 = (hi - lo) >> 1;
-    for (size_t i = threadIdx.x; i < n2; i += NT) d2[i] = s2[i];
-  }
+  mv_copy_chunk(img + (size_t)im * row_bytes, feats + (size_t)r * row_bytes, row_bytes, (size_t)blockIdx.y * chunk_bytes, chunk_bytes,
+                vec16, NT);
 }
 
 // ---------------------------------------------------------------------------------------------------- ranking
@@ -217,12 +203,6 @@ __global__ __launch_bounds__(NT) void rank_groups_kernel(const float* __restrict
   }
 }
 
-static inline void derive_keys(unsigned long long key, unsigned long long step, unsigned& k0, unsigned& k1) {
-  const unsigned long long kk = key ^ (step * 0x9E3779B97F4A7C15ULL);      // one stream per (key, step)
-  k0 = (unsigned)(kk & 0xffffffffULL);
-  k1 = (unsigned)(kk >> 32);
-}
-
 }  // namespace
 
 extern "C" int mv_pair_draws(unsigned long long key, unsigned long long step, int B, int D, uint32_t* draws, void* stream_) {
@@ -230,7 +210,7 @@ extern "C" int mv_pair_draws(unsigned long long key, unsigned long long step, in
   if (!draws || B <= 0 || D <= 0) return MV_E_ARG;
   if (D > MAX_DRAWS || (long long)B * MAX_DRAWS > 0x3fffffffLL) return MV_E_SHAPE;
   unsigned k0, k1;
-  derive_keys(key, step, k0, k1);
+  mv_derive_keys(key, step, k0, k1);
   const int n = B * D;
   pair_draws_kernel<<<(n + 255) / 256, 256, 0, stream>>>(k0, k1, B, D, draws);
   MV_CHECK_LAUNCH();
@@ -244,7 +224,7 @@ extern "C" int mv_pair_negatives(const int32_t* idx, int B, int n, const int32_t
   if (draws && n_draws <= 0) return MV_E_ARG;
   if ((long long)B * MAX_DRAWS > 0x3fffffffLL) return MV_E_SHAPE;          // 32-bit hash counters, int32 pair offsets
   unsigned k0, k1;
-  derive_keys(key, step, k0, k1);
+  mv_derive_keys(key, step, k0, k1);
   pair_negatives_kernel<<<(B + 255) / 256, 256, 0, stream>>>(idx, B, n, class_id, k0, k1, draws, n_draws, pairs, labels);
   MV_CHECK_LAUNCH();
   return MV_OK;

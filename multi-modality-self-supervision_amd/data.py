@@ -398,3 +398,72 @@ class RetrievalBank:
         cls_tok, sep_tok = self._tokens(R)
         desc = MaskDesc(out["desc"], T + N + 2, host=host)
         return cls_tok, out["input_txt"], desc, out["segment"], (out["feats"], out["pos"]), sep_tok
+
+
+# ---------------------------------------------------------------------------------------------------- report bank
+class ReportBank(RetrievalBank):
+    """A report-generation data set resident on the device, item i = (image i, report i): what seq2seq_finetune_batch builds per sample on
+    the host (Preprocess4Seq2seq, Downstream_task/report_generation_and_vqa/sc/data_loader.py:330-419) comes out of one
+    mv_report_assemble launch per batch, and an image passes the region encoder once, not once per epoch.
+      add_reports(ids, lengths)  ids int64 [n, T], each row tokens + [SEP] + [PAD]... (RetrievalBank.add_texts' layout); lengths [n] count
+                                 the [SEP].  Also fixes n_pred = min(max_pred, max(1, int(round((len - 1) * mask_prob)))) per item, with
+                                 Python's round as in the reference (1.5 -> 2, 4.5 -> 4), from the host copy of the lengths.
+      add_images(input_img)      as RetrievalBank.add_images
+      assemble(idx, mode, ...)   -> (cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, lists): the arguments of
+                                 CXRBertForReportFinetune.forward and lists = dict(masked_lm_labels, masked_pos, masked_weights) on the
+                                 device.  mode "s2s" / "bi" / "bar" (data_loader.py:395-412) or one per sample -- the reference draws the
+                                 pipeline per sample with random.choices (:282); that draw stays with the caller.  (key, step) select the
+                                 masking draw's random words; `draws` [B, T+1] overrides them (hip_ops.report_assemble).  idx given on the
+                                 host is checked against the bank there and the descriptors' host copy comes from the host lengths and
+                                 modes (no read-back); idx on the device (int32) is clamped into the bank by the kernel."""
+
+    def __init__(self, model=None, device=None, feat_dtype=None, max_pred=10, mask_prob=0.15):
+        super().__init__(model, device, feat_dtype)
+        self.max_pred, self.mask_prob = int(max_pred), float(mask_prob)
+        if self.max_pred < 1:
+            raise ValueError("ReportBank: max_pred >= 1")
+        self.n_pred = None
+
+    def add_reports(self, ids, lengths):
+        done = self.n_texts
+        self.add_texts(ids, lengths)
+        n_pred = torch.tensor([min(self.max_pred, max(1, int(round((ln - 1) * self.mask_prob)))) for ln in self._len_host[done:].tolist()],
+                              dtype=torch.int32).to(self.device)
+        self.n_pred = n_pred if self.n_pred is None else torch.cat([self.n_pred, n_pred])
+        return self
+
+    def assemble(self, idx, mode="s2s", key=0, step=0, draws=None):
+        from . import hip_ops as ops
+        n = self.n_texts
+        if n == 0 or self.n_images == 0:
+            raise ValueError("ReportBank.assemble: the bank is empty (add_reports, add_images)")
+        if n != self.n_images or self.n_pred is None or int(self.n_pred.numel()) != n:
+            raise ValueError(f"ReportBank.assemble: {n} reports (add_reports) and {self.n_images} images: item i is image i with report i")
+        host_idx = None
+        if torch.is_tensor(idx) and idx.device.type != "cpu":
+            if idx.dtype != torch.int32 or idx.dim() != 1:
+                raise TypeError("idx on the device: int32 [B]")
+            dev_idx = idx.contiguous()
+        else:
+            host_idx = torch.as_tensor(idx).reshape(-1)
+            if host_idx.numel() == 0 or host_idx.dtype.is_floating_point or host_idx.dtype == torch.bool:
+                raise ValueError("idx must be a non-empty integer list of bank items")
+            host_idx = host_idx.to(torch.int64)
+            if int(host_idx.min()) < 0 or int(host_idx.max()) >= n:
+                raise IndexError(f"idx outside the bank of {n} items")
+            dev_idx = host_idx.to(torch.int32).to(self.device)
+        B = int(dev_idx.numel())
+        modes = [mode] * B if isinstance(mode, str) else list(mode)
+        if len(modes) != B or any(m not in _S2S_FAMILY for m in modes):
+            raise ValueError(f"mode: one of {sorted(_S2S_FAMILY)}, or one per sample ({B})")
+        fam_host = torch.tensor([FAMILY_ID[_S2S_FAMILY[m]] for m in modes], dtype=torch.int32)
+        N, T = int(self.img_feats.shape[1]), int(self.txt_ids.shape[1])
+        host = None
+        if host_idx is not None:
+            host = torch.empty((B, 3), dtype=torch.int32)
+            host[:, 0], host[:, 1], host[:, 2] = fam_host, N + 2, N + 2 + self._len_host.index_select(0, host_idx)
+        out = ops.report_assemble(self.txt_ids, self.txt_len, self.n_pred, self.img_feats, self.img_pos, dev_idx, self.max_pred,
+                                  family=fam_host.to(self.device), key=key, step=step, draws=draws)
+        cls_tok, sep_tok = self._tokens(B)
+        lists = {k: out[k] for k in ("masked_lm_labels", "masked_pos", "masked_weights")}
+        return cls_tok, out["input_txt"], MaskDesc(out["desc"], T + N + 2, host=host), out["segment"], (out["feats"], out["pos"]), sep_tok, lists

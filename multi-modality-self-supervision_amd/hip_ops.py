@@ -954,3 +954,77 @@ def rank_groups(logits, labels, C, ks=(1, 5, 10), counters=None):
                                L.ptr(rank), L.ptr(counters), L.stream_ptr())
     L.check(rc, f"mv_rank_groups(G={n // C},C={C},ks={ks})")
     return p, pos, rank, counters
+
+
+# ---------------------------------------------------------------------------------------------------- report bank (csrc/mv_report.hip)
+def report_draws(key, step, B, T, device):
+    """int64 [B, T+1] holding the 32-bit words of the masking draw (see mv_report_draws): T shuffle keys and the coin per sample."""
+    out = torch.empty((B, T + 1), dtype=torch.int32, device=device)
+    L.require_cuda(out)
+    rc = _lib().mv_report_draws(int(key) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(B), int(T), L.ptr(out), L.stream_ptr())
+    L.check(rc, f"mv_report_draws(B={B},T={T})")
+    return _i32_to_words(out)
+
+
+def report_assemble(txt_ids, txt_len, n_pred, img_feats, img_pos, idx, max_pred, family=None, key=0, step=0, draws=None):
+    """Report fine-tuning batches from the banks (see mv_report_assemble): -> dict(input_txt, segment, desc, feats, pos, masked_pos,
+    masked_lm_labels, masked_weights).  draws: integers in [0, 2^32), [B, T+1], replacing the hash-generated words."""
+    L.require_cuda(txt_ids, txt_len, n_pred, img_feats, img_pos, idx, family)
+    if txt_ids.dtype != torch.int64 or txt_len.dtype != torch.int32 or n_pred.dtype != torch.int32 or img_pos.dtype != torch.int64 \
+            or idx.dtype != torch.int32 or (family is not None and family.dtype != torch.int32):
+        raise TypeError("report_assemble: txt_ids / img_pos int64, txt_len / n_pred / idx / family int32")
+    if txt_ids.dim() != 2 or img_feats.dim() != 3 or idx.dim() != 1:
+        raise ValueError("report_assemble: txt_ids [n_items, T], img_feats [n_items, N, F], idx [B]")
+    n, T = (int(s) for s in txt_ids.shape)
+    _, N, F = (int(s) for s in img_feats.shape)
+    B, dev = int(idx.numel()), txt_ids.device
+    if tuple(txt_len.shape) != (n,) or tuple(n_pred.shape) != (n,) or int(img_feats.shape[0]) != n or tuple(img_pos.shape) != (n, N) \
+            or (family is not None and tuple(family.shape) != (B,)):
+        raise ValueError("report_assemble: one length, prediction count, image and position row per item; one family per sample")
+    if not all(t.is_contiguous() for t in (txt_ids, txt_len, n_pred, img_feats, img_pos, idx) + (() if family is None else (family,))):
+        raise ValueError("report_assemble: contiguous tensors")
+    d32 = None
+    if draws is not None:
+        d32 = _words_to_i32(draws).to(dev).contiguous()
+        if tuple(d32.shape) != (B, T + 1):
+            raise ValueError(f"report_assemble: draws [B, T+1] = [{B}, {T + 1}]")
+    P = int(max_pred)
+    out = dict(input_txt=torch.empty((B, T), dtype=torch.int64, device=dev), segment=torch.empty((B, T), dtype=torch.int64, device=dev),
+               desc=torch.empty((B, 3), dtype=torch.int32, device=dev), feats=torch.empty((B, N, F), dtype=img_feats.dtype, device=dev),
+               pos=torch.empty((B, N), dtype=torch.int64, device=dev), masked_pos=torch.empty((B, P), dtype=torch.int64, device=dev),
+               masked_lm_labels=torch.empty((B, P), dtype=torch.int64, device=dev),
+               masked_weights=torch.empty((B, P), dtype=torch.float32, device=dev))
+    rc = _lib().mv_report_assemble(L.ptr(txt_ids), L.ptr(txt_len), L.ptr(n_pred), n, L.ptr(img_feats), L.dt_of(img_feats), L.ptr(img_pos),
+                                   L.ptr(idx), L.ptr(family), B, N, T, F, P, int(key) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF,
+                                   L.ptr(d32), L.ptr(out["input_txt"]), L.ptr(out["segment"]), L.ptr(out["desc"]), L.ptr(out["feats"]),
+                                   L.ptr(out["pos"]), L.ptr(out["masked_pos"]), L.ptr(out["masked_lm_labels"]),
+                                   L.ptr(out["masked_weights"]), L.stream_ptr())
+    L.check(rc, f"mv_report_assemble(B={B},N={N},T={T},F={F},max_pred={P})")
+    return out
+
+
+def report_plan(masked_pos, masked_lm_labels, masked_weights, L_seq, V, valid_len=None):
+    """report_finetune.build_plan on the device (see mv_report_plan): int64 [B, P] positions and labels, f32 [B, P] weights ->
+    dict(rows, row_ptr, labels, weights, sample, counts): full-size buffers (B P elements, row_ptr one more) of which the first
+    counts[0] rows / counts[1] entries are written; counts int32 [4] = {U, n, bad, 0}.  Nothing is read back here."""
+    L.require_cuda(masked_pos, masked_lm_labels, masked_weights, valid_len)
+    if masked_pos.dtype != torch.int64 or masked_lm_labels.dtype != torch.int64 or masked_weights.dtype != torch.float32 \
+            or (valid_len is not None and valid_len.dtype != torch.int32):
+        raise TypeError("report_plan: int64 positions and labels, f32 weights, int32 valid_len")
+    if masked_pos.dim() != 2 or masked_pos.shape != masked_lm_labels.shape or masked_pos.shape != masked_weights.shape:
+        raise ValueError("report_plan: positions, labels and weights share one [B, max_pred] shape")
+    B, P = (int(s) for s in masked_pos.shape)
+    if valid_len is not None and (valid_len.numel() != B or not valid_len.is_contiguous()):
+        raise ValueError("report_plan: valid_len [B]")
+    if not (masked_pos.is_contiguous() and masked_lm_labels.is_contiguous() and masked_weights.is_contiguous()):
+        raise ValueError("report_plan: contiguous tensors")
+    dev = masked_pos.device
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    out = dict(rows=i32(B * P), row_ptr=i32(B * P + 1), labels=i32(B * P), weights=torch.empty(B * P, dtype=torch.float32, device=dev),
+               sample=i32(B * P), counts=i32(4))
+    work = i32(3 * B)
+    rc = _lib().mv_report_plan(L.ptr(masked_pos), L.ptr(masked_lm_labels), L.ptr(masked_weights), L.ptr(valid_len), B, P, int(L_seq), int(V),
+                               L.ptr(work), L.ptr(out["rows"]), L.ptr(out["row_ptr"]), L.ptr(out["labels"]), L.ptr(out["weights"]),
+                               L.ptr(out["sample"]), L.ptr(out["counts"]), L.stream_ptr())
+    L.check(rc, f"mv_report_plan(B={B},P={P},L={L_seq},V={V})")
+    return out

@@ -100,7 +100,9 @@ class CXRBertForReportFinetune(TaskModel):
     (data_loader.py:353-419); host tensors (what a DataLoader hands over) are planned on the host, device tensors cost one read-back.
     model.lm_stats: f32 [4] on the device = [loss, kept weight sum, kept sample count, kept entries whose argmax is the label].
     `attn_mask`: a materialised 2-D / 3-D mask or data.MaskDesc (16-bit paths: the encoder then runs on the valid rows only).
-    .bert is the CXRBERT; there are no head Parameters.  `label_smoothing` as config.label_smoothing of the reference (0: plain CE)."""
+    .bert is the CXRBERT; there are no head Parameters.  `label_smoothing` as config.label_smoothing of the reference (0: plain CE).
+    fit_step / eval_step: the same objective from a device-resident data.ReportBank -- batch, masking draw and row plan built by HIP
+    kernels, one read-back per step (DESIGN.md "8q")."""
 
     # medvill_amd.optim.BertAdam: the encoder tensors this task's graph never reaches (`grad is None` in the reference)
     _unreached = ("itm.", "enc.pooler.")
@@ -125,6 +127,7 @@ class CXRBertForReportFinetune(TaskModel):
         dev = eng.device
         B, U = plan["B"], plan["U"]
         pack = self._pack(attn_mask)
+        # (a host plan -- build_plan's -- is uploaded here; a device plan -- mv_report_plan's, fit_step / eval_step -- stays where it is)
         d = {k_: plan[k_].to(dev) for k_ in ("rows", "row_ptr", "labels", "weights", "sample")}
         eng.encoder_forward(cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, pack=pack, tail_rows=d["rows"])
         S, V = eng.S, self.bert.cfg.vocab_size
@@ -188,6 +191,58 @@ class CXRBertForReportFinetune(TaskModel):
             self._prepare(want_grad)
             loss = _ReportFn.apply(self, plan, k, cls_tok, input_txt, attn_mask, segment, feats, pos, sep_tok, *self.bert._plist)
         return loss, loss.new_zeros(1)           # (masked_lm_loss, dummy_value), model.py:1054
+
+    # ------------------------------------------------------------------ steps from a device-resident bank
+    def _bank_loss(self, bank, idx, step, key, mode, drop_worst_ratio, draws):
+        """data.ReportBank.assemble -> mv_report_plan -> the _ReportFn node on the device plan (the caller has set the engine state).
+        ONE read-back: the plan's counts {U, n, bad} -- the engine sizes its launches with U on the host."""
+        cfg = self.bert.cfg
+        if bank.n_texts and bank.n_images:
+            Lq = int(bank.img_feats.shape[1]) + int(bank.txt_ids.shape[1]) + 2
+            if Lq > cfg.max_pos:
+                raise ValueError(f"the bank's sequences hold {Lq} positions ([CLS] + regions + [SEP] + text), max_position_embeddings is "
+                                 f"{cfg.max_pos}")
+        cls_tok, input_txt, desc, segment, (feats, pos), sep_tok, lists = bank.assemble(idx, mode=mode, key=key, step=step, draws=draws)
+        B = int(input_txt.shape[0])
+        k = keep_count(B, drop_worst_ratio)
+        if not 0 <= k <= B:
+            raise ValueError(f"drop_worst_ratio {drop_worst_ratio} keeps {k} of {B} samples")
+        dp = ops.report_plan(lists["masked_pos"], lists["masked_lm_labels"], lists["masked_weights"], desc.L, cfg.vocab_size,
+                             valid_len=desc.desc[:, 2].contiguous() if self._pack(desc) else None)
+        U, n, bad, _ = dp["counts"].tolist()
+        if bad:
+            raise ValueError(f"{bad} listed predictions are refused (report_finetune.build_plan: position 0, a position outside the "
+                             "sequence or past the sample's valid length, a label outside the vocabulary, a negative or non-finite weight)")
+        plan = dict(B=B, U=U, n=n, rows=dp["rows"][:U], row_ptr=dp["row_ptr"][:U + 1], labels=dp["labels"][:n], weights=dp["weights"][:n],
+                    sample=dp["sample"][:n])
+        return _ReportFn.apply(self, plan, k, cls_tok, input_txt, desc, segment, feats, pos, sep_tok, *self.bert._plist)
+
+    def fit_step(self, bank, idx, optimizer, step, key=0, mode="s2s", drop_worst_ratio=0.0, draws=None):
+        """One fine-tuning step (finetune.py:430-469) from a data.ReportBank: the masked batch of the items `idx` (one mv_report_assemble
+        launch; (key, step) select the masking draw, `draws` overrides it), the row plan on the device, the objective, its backward
+        (run_backward: an overflowed f16 backward is redone at a smaller loss scale) and optimizer.step().  `optimizer`: a
+        medvill_amd.optim.BertAdam over model.parameters(); its gradients are cleared first.  mode: "s2s" / "bi" / "bar" or one per
+        sample.  Returns the loss as a device scalar.  Refused: several ranks, an empty bank, a bank whose halves differ in size, a host
+        idx outside the bank (IndexError), sequences longer than max_position_embeddings."""
+        check_single_rank("CXRBertForReportFinetune", "data-parallel fine-tuning is not supported (drop-worst selects over the whole "
+                          "batch and the gradients would not be all-reduced); fine-tune on one rank, or run eval_step")
+        with self._engine_state("training", "keep_acts"):
+            optimizer.zero_grad()
+            with torch.enable_grad():
+                self._prepare(True)
+                loss = self._bank_loss(bank, idx, step, key, mode, drop_worst_ratio, draws)
+                loss.backward()
+        optimizer.step()
+        return loss.detach()
+
+    @torch.no_grad()
+    def eval_step(self, bank, idx, step, key=0, mode="s2s", drop_worst_ratio=0.0, draws=None):
+        """The loss of fit_step's batch in eval mode, without gradients; the engine's training / keep-activations / dropout-counter state
+        is restored.  model.lm_stats holds the kept weight sum, sample count and argmax hits as after forward."""
+        with self._engine_state("training", "keep_acts", "drop_counter") as eng:
+            self._prepare(False)
+            eng.training = False
+            return self._bank_loss(bank, idx, step, key, mode, drop_worst_ratio, draws)
 
     def generate(self, cls_tok, input_img, sep_tok, **kw):
         """CXRBERT.generate of the weights being fine-tuned (validation decoding; eval mode, no gradients, engine state restored)."""
