@@ -724,6 +724,42 @@ int mv_report_plan(const int64_t* pos, const int64_t* labels, const float* weigh
                    int32_t* work, int32_t* rows, int32_t* row_ptr, int32_t* out_labels, float* out_weights, int32_t* out_sample,
                    int32_t* counts, void* stream);
 
+/* ---- VQA fine-tuning and evaluation from a device-resident question bank (csrc/mv_vqa_bank.hip) ------------------------------
+ * The reference's VQA-RAD loader (Downstream_task/report_generation_and_vqa/sc/data_loader.py:236-273: many questions per image, a
+ * sparse soft answer per question), its Preprocess4Seq2seq for questions (:340-392) and the score of compute_score_with_logits
+ * (pytorch_pretrained_bert/model.py:1007-1023).  Additive entry points.
+ *
+ * The bank: txt_ids int64 [n_questions, T] (each row tokens + [SEP] + [PAD]...), txt_len int32 [n_questions] (counting the [SEP];
+ *     clamped to [1, T]), q_img int32 [n_questions] (the question's image; clamped to [0, n_images)), the answers in CSR form --
+ *     ans_ptr int32 [n_questions + 1], ans_label int32 [nnz], ans_score f32 [nnz] (both nullable when nnz = 0; offsets are clamped to
+ *     [0, nnz]) --, ans_type int32 [n_questions] (0 closed, 1 open, anything else neither), img_feats [n_images, N, F] (dtype),
+ *     img_pos int64 [n_images, N].
+ * mv_vqa_assemble: one launch per batch, grid (B, chunks of the N F feature row).  idx int32 [B] (an index outside the bank is clamped
+ *     into it), family int32 [B] (nullable = 4, the 1-D family).  For slot i with question d = idx[i], image m = q_img[d] and
+ *     len = txt_len[d] it writes input_txt int64 [B, T] (the bank row as it is: VQA masks nothing), segment int64 [B, T] (1 for
+ *     t < len, else 0), desc int32 [B, 3] = {family, N+2, N+2+len}, feats [B, N, F] (dtype) = img_feats[m] bit for bit, pos_out int64
+ *     [B, N] = img_pos[m], target f32 [B, A] = zeros with target[i, ans_label[e]] = ans_score[e] for e = ans_ptr[d] .. ans_ptr[d+1]-1
+ *     in that order (a later duplicate of a label wins, as target.scatter_(0, labels, scores) on the CPU; a label outside [0, A) is
+ *     skipped), ans_type_out int32 [B] = ans_type[d].  No atomics: fully defined and bitwise reproducible.  T <= 1024, N F < 2^31,
+ *     B T < 2^31.
+ * mv_vqa_score: pred int64 [B] (an answer column: arg_train or arg_infer of mv_bce_fwd_bwd), idx int32 [B] (clamped), group int32
+ *     [n_questions] (nullable = group 0; clamped to [0, G)), G <= 8.  s = ans_score of the LAST entry of question idx[i] whose label
+ *     equals pred[i], else 0: the dense target's value at the predicted column.  score f32 [B] (nullable) = s.  counters uint64
+ *     [G, 3, 2], ACCUMULATED (zero them first): for the sample's group g and type slot t (0 closed, 1 open, 2 neither) it adds
+ *     {fx(s), 1} to counters[g, t]; fx(x) = rint(x * 2^32) of the value widened to f64 (two's complement when negative), so the sums
+ *     are integers and do not depend on the order in which samples finish.
+ * Null pointers (family, group, score, and ans_label / ans_score at nnz = 0, excepted), non-positive sizes, nnz < 0: MV_E_ARG; unknown
+ * dtype: MV_E_DTYPE; G > 8, T > 1024, N F or B T past 32-bit indexing: MV_E_SHAPE.  All of it is checked before anything touches the
+ * HIP runtime.  */
+int mv_vqa_assemble(const int64_t* txt_ids, const int32_t* txt_len, const int32_t* q_img, int n_questions, const int32_t* ans_ptr,
+                    const int32_t* ans_label, const float* ans_score, int nnz, const int32_t* ans_type, const void* img_feats, int dtype,
+                    const int64_t* img_pos, int n_images, const int32_t* idx, const int32_t* family, int B, int N, int T, int F, int A,
+                    int64_t* input_txt, int64_t* segment, int32_t* desc, void* feats, int64_t* pos_out, float* target,
+                    int32_t* ans_type_out, void* stream);
+int mv_vqa_score(const int64_t* pred, const int32_t* idx, int B, int n_questions, const int32_t* ans_ptr, const int32_t* ans_label,
+                 const float* ans_score, int nnz, const int32_t* ans_type, const int32_t* group, int G, float* score,
+                 unsigned long long* counters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

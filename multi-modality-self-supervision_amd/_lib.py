@@ -108,6 +108,9 @@ PROTOTYPES = {
     "mv_report_draws": [u64, u64, i32, i32, vp, vp],
     "mv_report_assemble": [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "mv_report_plan": [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    # VQA from a device-resident question bank (csrc/mv_vqa_bank.hip)
+    "mv_vqa_assemble": [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "mv_vqa_score": [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp],
 }
 # include/medvill_debug.h: exported by libmedvill_hip_dbg.so only
 DEBUG_PROTOTYPES = {"mv_debug_set_knob": [i32, i32], "mv_debug_get_knob": [i32]}

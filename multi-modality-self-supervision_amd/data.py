@@ -467,3 +467,166 @@ class ReportBank(RetrievalBank):
         cls_tok, sep_tok = self._tokens(B)
         lists = {k: out[k] for k in ("masked_lm_labels", "masked_pos", "masked_weights")}
         return cls_tok, out["input_txt"], MaskDesc(out["desc"], T + N + 2, host=host), out["segment"], (out["feats"], out["pos"]), sep_tok, lists
+
+
+# ---------------------------------------------------------------------------------------------------- VQA bank
+VQA_GROUPS = 8                     # mv_vqa_score's group slots
+_ANS_TYPE = {"CLOSED": 0, "CLOSED ": 0, "OPEN": 1, "OPEN ": 1}          # data_loader.py:434-437
+
+
+def vqa_answer_type(t) -> int:
+    """0 (closed) / 1 (open) from an integer or the reference's strings (data_loader.py:434-437, with their trailing-space variants);
+    anything else is 2, which neither split counts."""
+    if isinstance(t, str):
+        return _ANS_TYPE.get(t, 2)
+    if torch.is_tensor(t):
+        t = t.item()
+    try:
+        v = int(t)
+    except (TypeError, ValueError):
+        return 2
+    return v if v in (0, 1) and v == t else 2
+
+
+class VqaBank(RetrievalBank):
+    """A VQA data set resident on the device: question i = (image q_img[i], question i, its sparse soft answers, its answer type, its
+    group).  Many questions share one image (VQA-RAD: 315 images for 3,064 training questions, data_loader.py:236-273), so an image
+    passes the region encoder once, not once per question, and a batch comes out of one mv_vqa_assemble launch.
+      add_images(input_img)   as RetrievalBank.add_images, once per distinct image
+      add_questions(ids, lengths, image_item, labels, scores, ans_type, group=None)
+                              ids int64 [n, T] / lengths [n]: add_texts' layout (tokens + [SEP] + [PAD]..., lengths count the [SEP]);
+                              image_item int [n]: the item of the image bank; labels[i] / scores[i]: the answer['labels'] /
+                              answer['scores'] sequences of the reference's target files -- ragged, possibly empty or None (an all-zero
+                              target, :269-271), a label listed twice keeps its later score like target.scatter_ on the CPU;
+                              ans_type[i]: 0 / 1 or the reference's strings (vqa_answer_type); group[i] in [0, 8): the reference's
+                              --vqa_rad organ subsets (:180-187), None = group 0.  Refused (ValueError, nothing is added): a label
+                              outside [0, n_answers), labels and scores of different length, a score that is not finite, a group
+                              outside [0, 8), a negative image item.
+      assemble(idx, mode)     -> (cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, ans_labels, ans_type): the arguments of
+                              CXRBertForVQA.forward with attn_mask a MaskDesc.  mode "s2s" / "bi" / "bar" or one per sample
+                              (ReportBank.assemble's rule; the reference's per-sample draw, :282, stays with the caller).  idx given on
+                              the host is checked there (IndexError outside the bank, ValueError when a listed question names an image
+                              the image bank does not hold) and the descriptors' host copy comes from the host lengths (no read-back);
+                              idx on the device (int32) is clamped into the bank by the kernel.
+      dense_targets(idx)      f32 [len(idx), n_answers] built on the host with scatter_: the restated reference (:269-271).
+    Storage on the device: q_img int32 [n], ans_ptr int32 [n+1], ans_label int32 [nnz], ans_score f32 [nnz], ans_type int32 [n], group
+    int32 [n]; host copies of the lengths, q_img and the answers."""
+
+    def __init__(self, model=None, device=None, feat_dtype=None, n_answers=458):
+        super().__init__(model, device, feat_dtype)
+        self.n_answers = int(n_answers)
+        if self.n_answers < 1:
+            raise ValueError("VqaBank: n_answers >= 1")
+        self.q_img = self.ans_label = self.ans_score = self.ans_type = self.group = None
+        self.ans_ptr = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._q_img_host = torch.zeros(0, dtype=torch.int64)
+        self._ptr_host = torch.zeros(1, dtype=torch.int64)
+        self._label_host = torch.zeros(0, dtype=torch.int64)
+        self._score_host = torch.zeros(0, dtype=torch.float32)
+
+    @property
+    def n_questions(self):
+        return 0 if self.q_img is None else int(self.q_img.numel())
+
+    def add_questions(self, ids, lengths, image_item, labels, scores, ans_type, group=None):
+        ids = torch.as_tensor(ids)
+        n = int(ids.shape[0]) if ids.dim() == 2 else -1
+        img = torch.as_tensor(image_item).reshape(-1)
+        if n < 1 or img.numel() != n or len(labels) != n or len(scores) != n or len(ans_type) != n or (group is not None and len(group) != n):
+            raise ValueError("add_questions: ids [n, T] and one image item, label list, score list, answer type (and group) per question")
+        if img.dtype.is_floating_point or img.dtype == torch.bool or int(img.min()) < 0:
+            raise ValueError("add_questions: image_item holds non-negative integers")
+        lab, sc, ptr = [], [], [int(self._ptr_host[-1])]
+        for i in range(n):
+            li = [] if labels[i] is None else torch.as_tensor(labels[i]).reshape(-1).tolist()
+            si = [] if scores[i] is None else torch.as_tensor(scores[i], dtype=torch.float32).reshape(-1).tolist()
+            if len(li) != len(si):
+                raise ValueError(f"add_questions: question {i} lists {len(li)} labels and {len(si)} scores")
+            if any(int(l) != l or not 0 <= int(l) < self.n_answers for l in li):
+                raise ValueError(f"add_questions: question {i} lists a label outside [0, {self.n_answers})")
+            lab += [int(l) for l in li]
+            sc += si
+            ptr.append(ptr[0] + len(lab))
+        sc = torch.tensor(sc, dtype=torch.float32)
+        if not bool(torch.isfinite(sc).all()):
+            raise ValueError("add_questions: a score is not finite")
+        if ptr[-1] > 2 ** 31 - 1:
+            raise ValueError("add_questions: more than 2^31 - 1 answers")
+        grp = torch.zeros(n, dtype=torch.int64) if group is None else torch.as_tensor(group).reshape(-1).to(torch.int64)
+        if int(grp.min()) < 0 or int(grp.max()) >= VQA_GROUPS:
+            raise ValueError(f"add_questions: a group outside [0, {VQA_GROUPS})")
+        typ = torch.tensor([vqa_answer_type(t) for t in ans_type], dtype=torch.int32)
+        self.add_texts(ids, lengths)                         # (its own refusals come before anything of the questions is stored)
+        lab = torch.tensor(lab, dtype=torch.int64)
+        self._q_img_host = torch.cat([self._q_img_host, img.to(torch.int64).cpu()])
+        self._ptr_host = torch.cat([self._ptr_host, torch.tensor(ptr[1:], dtype=torch.int64)])
+        self._label_host, self._score_host = torch.cat([self._label_host, lab]), torch.cat([self._score_host, sc])
+        cat = lambda old, new: new if old is None else torch.cat([old, new])
+        dev32 = lambda t: t.to(torch.int32).to(self.device).contiguous()
+        self.q_img = cat(self.q_img, dev32(img))
+        self.ans_label, self.ans_score = cat(self.ans_label, dev32(lab)), cat(self.ans_score, sc.to(self.device))
+        self.ans_type, self.group = cat(self.ans_type, typ.to(self.device)), cat(self.group, dev32(grp))
+        self.ans_ptr = dev32(self._ptr_host)
+        return self
+
+    def dense_targets(self, idx):
+        idx = torch.as_tensor(idx).reshape(-1).to(torch.int64).cpu()
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.n_questions):
+            raise IndexError(f"idx outside the bank of {self.n_questions} questions")
+        out = torch.zeros((idx.numel(), self.n_answers), dtype=torch.float32)
+        for i, d in enumerate(idx.tolist()):
+            e0, e1 = int(self._ptr_host[d]), int(self._ptr_host[d + 1])
+            if e1 > e0:
+                out[i].scatter_(0, self._label_host[e0:e1], self._score_host[e0:e1])
+        return out
+
+    def _check_filled(self):
+        n = self.n_questions
+        if n == 0 or self.n_images == 0:
+            raise ValueError("VqaBank: the bank is empty (add_questions, add_images)")
+        if n != self.n_texts:
+            raise ValueError(f"VqaBank: {self.n_texts} text rows for {n} questions: fill the bank with add_questions, not add_texts")
+
+    def host_idx(self, idx):
+        """A host index list, checked against both banks: -> int64 [B]."""
+        self._check_filled()
+        h = torch.as_tensor(idx).reshape(-1)
+        if h.numel() == 0 or h.dtype.is_floating_point or h.dtype == torch.bool:
+            raise ValueError("idx must be a non-empty integer list of questions")
+        h = h.to(torch.int64)
+        if int(h.min()) < 0 or int(h.max()) >= self.n_questions:
+            raise IndexError(f"idx outside the bank of {self.n_questions} questions")
+        if int(self._q_img_host.index_select(0, h).max()) >= self.n_images:
+            raise ValueError(f"a listed question names an image outside the image bank of {self.n_images}")
+        return h
+
+    def host_descriptors(self, host_idx, fam_host):
+        """int32 [B, 3] = {family, N+2, N+2+len}: what mv_vqa_assemble writes, from the host copy of the lengths."""
+        N = int(self.img_feats.shape[1])
+        d = torch.empty((host_idx.numel(), 3), dtype=torch.int32)
+        d[:, 0], d[:, 1], d[:, 2] = fam_host, N + 2, N + 2 + self._len_host.index_select(0, host_idx)
+        return d
+
+    def assemble(self, idx, mode="bi"):
+        from . import hip_ops as ops
+        host_idx = None
+        if torch.is_tensor(idx) and idx.device.type != "cpu":
+            self._check_filled()
+            if idx.dtype != torch.int32 or idx.dim() != 1:
+                raise TypeError("idx on the device: int32 [B]")
+            dev_idx = idx.contiguous()
+        else:
+            host_idx = self.host_idx(idx)
+            dev_idx = host_idx.to(torch.int32).to(self.device)
+        B = int(dev_idx.numel())
+        modes = [mode] * B if isinstance(mode, str) else list(mode)
+        if len(modes) != B or any(m not in _S2S_FAMILY for m in modes):
+            raise ValueError(f"mode: one of {sorted(_S2S_FAMILY)}, or one per sample ({B})")
+        fam_host = torch.tensor([FAMILY_ID[_S2S_FAMILY[m]] for m in modes], dtype=torch.int32)
+        host = None if host_idx is None else self.host_descriptors(host_idx, fam_host)
+        out = ops.vqa_assemble(self.txt_ids, self.txt_len, self.q_img, self.ans_ptr, self.ans_label, self.ans_score, self.ans_type,
+                               self.img_feats, self.img_pos, dev_idx, self.n_answers, family=fam_host.to(self.device))
+        N, T = int(self.img_feats.shape[1]), int(self.txt_ids.shape[1])
+        cls_tok, sep_tok = self._tokens(B)
+        return (cls_tok, out["input_txt"], MaskDesc(out["desc"], T + N + 2, host=host), out["segment"], (out["feats"], out["pos"]), sep_tok,
+                out["target"], out["ans_type"])

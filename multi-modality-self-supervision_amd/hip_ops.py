@@ -1028,3 +1028,71 @@ def report_plan(masked_pos, masked_lm_labels, masked_weights, L_seq, V, valid_le
                                L.ptr(out["sample"]), L.ptr(out["counts"]), L.stream_ptr())
     L.check(rc, f"mv_report_plan(B={B},P={P},L={L_seq},V={V})")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- VQA bank (csrc/mv_vqa_bank.hip)
+VQA_MAX_GROUPS = 8        # mv_vqa_score's counters: uint64 [G, 3, 2], G <= 8 (include/medvill.h)
+
+
+def _vqa_csr_check(who, n, ans_ptr, ans_label, ans_score, ans_type):
+    if ans_ptr.dtype != torch.int32 or ans_label.dtype != torch.int32 or ans_score.dtype != torch.float32 or ans_type.dtype != torch.int32:
+        raise TypeError(f"{who}: ans_ptr / ans_label / ans_type int32, ans_score f32")
+    if tuple(ans_ptr.shape) != (n + 1,) or tuple(ans_type.shape) != (n,) or ans_label.dim() != 1 or ans_label.shape != ans_score.shape:
+        raise ValueError(f"{who}: ans_ptr [n+1], ans_label / ans_score [nnz], ans_type [n]")
+    if not all(t.is_contiguous() for t in (ans_ptr, ans_label, ans_score, ans_type)):
+        raise ValueError(f"{who}: contiguous tensors")
+    return int(ans_label.numel())
+
+
+def vqa_assemble(txt_ids, txt_len, q_img, ans_ptr, ans_label, ans_score, ans_type, img_feats, img_pos, idx, n_answers, family=None):
+    """VQA batches from the question bank (see mv_vqa_assemble): -> dict(input_txt, segment, desc, feats, pos, target, ans_type)."""
+    L.require_cuda(txt_ids, txt_len, q_img, ans_ptr, ans_label, ans_score, ans_type, img_feats, img_pos, idx, family)
+    if txt_ids.dtype != torch.int64 or txt_len.dtype != torch.int32 or q_img.dtype != torch.int32 or img_pos.dtype != torch.int64 \
+            or idx.dtype != torch.int32 or (family is not None and family.dtype != torch.int32):
+        raise TypeError("vqa_assemble: txt_ids / img_pos int64, txt_len / q_img / idx / family int32")
+    if txt_ids.dim() != 2 or img_feats.dim() != 3 or idx.dim() != 1:
+        raise ValueError("vqa_assemble: txt_ids [n_questions, T], img_feats [n_images, N, F], idx [B]")
+    n, T = (int(s) for s in txt_ids.shape)
+    n_img, N, F = (int(s) for s in img_feats.shape)
+    B, A, dev = int(idx.numel()), int(n_answers), txt_ids.device
+    nnz = _vqa_csr_check("vqa_assemble", n, ans_ptr, ans_label, ans_score, ans_type)
+    if tuple(txt_len.shape) != (n,) or tuple(q_img.shape) != (n,) or tuple(img_pos.shape) != (n_img, N) \
+            or (family is not None and tuple(family.shape) != (B,)):
+        raise ValueError("vqa_assemble: one length and image per question, one position row per image, one family per sample")
+    if not all(t.is_contiguous() for t in (txt_ids, txt_len, q_img, img_feats, img_pos, idx) + (() if family is None else (family,))):
+        raise ValueError("vqa_assemble: contiguous tensors")
+    out = dict(input_txt=torch.empty((B, T), dtype=torch.int64, device=dev), segment=torch.empty((B, T), dtype=torch.int64, device=dev),
+               desc=torch.empty((B, 3), dtype=torch.int32, device=dev), feats=torch.empty((B, N, F), dtype=img_feats.dtype, device=dev),
+               pos=torch.empty((B, N), dtype=torch.int64, device=dev), target=torch.empty((B, A), dtype=torch.float32, device=dev),
+               ans_type=torch.empty((B,), dtype=torch.int32, device=dev))
+    rc = _lib().mv_vqa_assemble(L.ptr(txt_ids), L.ptr(txt_len), L.ptr(q_img), n, L.ptr(ans_ptr), L.ptr(ans_label) or None,
+                                L.ptr(ans_score) or None, nnz, L.ptr(ans_type), L.ptr(img_feats), L.dt_of(img_feats), L.ptr(img_pos), n_img,
+                                L.ptr(idx), L.ptr(family), B, N, T, F, A, L.ptr(out["input_txt"]), L.ptr(out["segment"]), L.ptr(out["desc"]),
+                                L.ptr(out["feats"]), L.ptr(out["pos"]), L.ptr(out["target"]), L.ptr(out["ans_type"]), L.stream_ptr())
+    L.check(rc, f"mv_vqa_assemble(B={B},N={N},T={T},F={F},A={A})")
+    return out
+
+
+def vqa_score(pred, idx, ans_ptr, ans_label, ans_score, ans_type, group=None, G=VQA_MAX_GROUPS, counters=None, want_score=True):
+    """The score of predicted answer columns against the bank's sparse answers (see mv_vqa_score): pred int64 [B], idx int32 [B] ->
+    (score f32 [B] or None, counters int64 [G, 3, 2] = {sum of fx(score), samples} by group and type slot closed / open / neither);
+    `counters` (on the device) is accumulated into when given."""
+    L.require_cuda(pred, idx, ans_ptr, ans_label, ans_score, ans_type, group, counters)
+    if pred.dtype != torch.int64 or idx.dtype != torch.int32 or (group is not None and group.dtype != torch.int32):
+        raise TypeError("vqa_score: pred int64, idx / group int32")
+    B, n, G = int(pred.numel()), int(ans_type.numel()), int(G)
+    if pred.dim() != 1 or tuple(idx.shape) != (B,) or not pred.is_contiguous() or not idx.is_contiguous():
+        raise ValueError("vqa_score: contiguous pred [B] and idx [B]")
+    nnz = _vqa_csr_check("vqa_score", n, ans_ptr, ans_label, ans_score, ans_type)
+    if group is not None and (tuple(group.shape) != (n,) or not group.is_contiguous()):
+        raise ValueError("vqa_score: group [n_questions]")
+    dev = pred.device
+    if counters is None:
+        counters = torch.zeros((max(G, 1), 3, 2), dtype=torch.int64, device=dev)
+    elif counters.dtype != torch.int64 or counters.numel() != G * 6 or not counters.is_contiguous():
+        raise TypeError(f"vqa_score: counters int64 [{G}, 3, 2]")
+    score = torch.empty(B, dtype=torch.float32, device=dev) if want_score else None
+    rc = _lib().mv_vqa_score(L.ptr(pred), L.ptr(idx), B, n, L.ptr(ans_ptr), L.ptr(ans_label) or None, L.ptr(ans_score) or None, nnz,
+                             L.ptr(ans_type), L.ptr(group), G, L.ptr(score), L.ptr(counters), L.stream_ptr())
+    L.check(rc, f"mv_vqa_score(B={B},G={G})")
+    return score, counters

@@ -44,6 +44,26 @@ def head_layout(H: int, A: int):
     return lay, off, Ap
 
 
+def vqa_metrics(counters) -> dict:
+    """mv_vqa_score's integer counters [G, 3, 2] = {sum of fx(score), samples} by group and type slot (closed, open, neither) -> the
+    reference's numbers, formed in f64 from exact integer sums: dict(acc, closed_acc, open_acc, n, closed_n, open_n, by_group {g: the
+    same six, for the groups that have samples}).  acc counts every sample, the two splits their own; a split without samples is nan."""
+    c = torch.as_tensor(counters).to(torch.int64).reshape(-1, 3, 2).tolist()
+
+    def ratio(fx, cnt):
+        return fx / 4294967296.0 / cnt if cnt else float("nan")
+
+    def six(groups):
+        fx = [sum(g[t][0] for g in groups) for t in range(3)]
+        cnt = [sum(g[t][1] for g in groups) for t in range(3)]
+        return dict(acc=ratio(sum(fx), sum(cnt)), closed_acc=ratio(fx[0], cnt[0]), open_acc=ratio(fx[1], cnt[1]), n=sum(cnt),
+                    closed_n=cnt[0], open_n=cnt[1])
+
+    out = six(c)
+    out["by_group"] = {g: six([row]) for g, row in enumerate(c) if sum(t[1] for t in row)}
+    return out
+
+
 class _VQAFn(torch.autograd.Function):
     """Encoder + answer classifier (+ BCE) as one autograd node.  mode "loss": -> mean BCE (the reference's vqa_loss); mode "logits":
     -> logits [B, A].  The backward runs the classifier's backward into the compact [B, H] hidden-state gradient, then the encoder's."""
@@ -80,7 +100,9 @@ class CXRBertForVQA(FlatHead):
           neither -> differentiable logits [B, A] of the [CLS] row
     .bert is the CXRBERT; .ans_classifier the Sequential(Linear, ReLU, Linear) whose Parameters are views of the classifier's flat buffer
     (task.FlatHead).
-    `attn_mask` may be a materialised mask or data.MaskDesc descriptors (16-bit: the encoder then runs on the valid rows only)."""
+    `attn_mask` may be a materialised mask or data.MaskDesc descriptors (16-bit: the encoder then runs on the valid rows only).
+    fit_step / evaluate: the same step, and the reference's whole-set evaluation with its closed / open split, from a device-resident
+    data.VqaBank -- the batch built by one HIP launch, one read-back per evaluation (DESIGN.md "8r")."""
 
     # medvill_amd.optim.BertAdam: the classifier's tensors, and the encoder tensors the VQA graph never reaches (`grad is None` in the
     # reference: no update, no weight decay)
@@ -234,6 +256,86 @@ class CXRBertForVQA(FlatHead):
             ans = torch.empty(int(input_txt.shape[0]), dtype=torch.int64, device=eng.device)
             ops.bce_fwd_bwd(logits, self.n_answers, ld=self.Ap, arg_infer=ans)
         return ans
+
+    # ------------------------------------------------------------------ steps from a device-resident bank
+    def _check_bank(self, bank):
+        if bank.n_questions == 0 or bank.n_images == 0:
+            raise ValueError("the bank is empty (VqaBank.add_questions, add_images)")
+        if bank.n_answers != self.n_answers:
+            raise ValueError(f"the bank holds targets over {bank.n_answers} answers, the classifier has {self.n_answers}")
+        Lq = int(bank.img_feats.shape[1]) + int(bank.txt_ids.shape[1]) + 2
+        if Lq > self.bert.cfg.max_pos:
+            raise ValueError(f"the bank's sequences hold {Lq} positions ([CLS] + regions + [SEP] + text), max_position_embeddings is "
+                             f"{self.bert.cfg.max_pos}")
+
+    def fit_step(self, bank, idx, optimizer, mode="bi"):
+        """One fine-tuning step (finetune.py:430-469, tasks='vqa') from a data.VqaBank: optimizer.zero_grad(), the batch of the questions
+        `idx` (one mv_vqa_assemble launch), the loss node of forward, its backward and optimizer.step().  mode: "s2s" / "bi" / "bar" or
+        one per sample.  Returns the loss as a device scalar; vqa_stats / vqa_pred are set as after forward.  Refused: several ranks,
+        an empty bank, a bank over another answer count, sequences longer than max_position_embeddings, a host idx outside the bank
+        (IndexError)."""
+        check_single_rank("CXRBertForVQA", "data-parallel VQA fine-tuning is not supported (the classifier's gradients would not be "
+                          "all-reduced); fine-tune on one rank, or run evaluate")
+        self._check_bank(bank)
+        with self._engine_state("training", "keep_acts"):
+            optimizer.zero_grad()
+            with torch.enable_grad():
+                cls_tok, input_txt, desc, segment, img, sep_tok, target, ans_type = bank.assemble(idx, mode=mode)
+                _, loss = self(cls_tok, input_txt, desc, segment, img, sep_tok, ans_labels=target, ans_type=ans_type)
+                loss.backward()
+        optimizer.step()
+        return loss.detach()
+
+    @torch.no_grad()
+    def evaluate(self, bank, idx=None, batch_size=64, path="inference", mode="bi"):
+        """The reference's evaluation over the questions `idx` of a data.VqaBank (None: every question, in order), in eval mode and
+        without gradients; a last partial batch is allowed.  path "inference": the [CLS] (.) image-[SEP] vector and the argmax over
+        columns 1.. (model.py:979-983); "train": the [CLS] vector, the argmax over all columns and the BCE sum (model.py:1020-1023).
+        Every batch's predictions go into one device buffer, one mv_vqa_score launch scores them against the bank's sparse answers and
+        sums them by group and closed / open split; ONE read-back at the end.  -> dict(acc, closed_acc, open_acc, n, closed_n, open_n,
+        by_group {g: the same six numbers, for the groups that have samples}, loss (path "train": the mean BCE over n * A elements),
+        pred int64 [n] and score f32 [n] on the device).  A split without samples has accuracy nan.  The engine's training /
+        keep-activations / dropout-counter state is restored."""
+        if path not in ("inference", "train"):
+            raise ValueError(f"path {path!r}: 'inference' or 'train'")
+        if int(batch_size) < 1:
+            raise ValueError("batch_size >= 1")
+        self._check_bank(bank)
+        eng = self.bert.engine
+        # `take`: what the batches are cut from -- a host list stays a host list (its descriptors need no read-back)
+        if torch.is_tensor(idx) and idx.device.type != "cpu":
+            if idx.dtype != torch.int32 or idx.dim() != 1 or idx.numel() == 0:
+                raise TypeError("idx on the device: non-empty int32 [n]")
+            dev_idx = take = idx.contiguous()
+        else:
+            take = bank.host_idx(torch.arange(bank.n_questions) if idx is None else idx)
+            dev_idx = take.to(torch.int32).to(eng.device)
+        n, A, bs = int(dev_idx.numel()), self.n_answers, int(batch_size)
+        if not isinstance(mode, str) and len(mode) != n:
+            raise ValueError(f"mode: one name, or one per question ({n})")
+        pred = torch.empty(n, dtype=torch.int64, device=eng.device)
+        stats = torch.zeros(6, dtype=torch.float32, device=eng.device)
+        with self._engine_state("training", "keep_acts", "drop_counter"):
+            self._prepare(False)
+            eng.training = False
+            for s in range(0, n, bs):
+                e = min(n, s + bs)
+                cls_tok, input_txt, desc, segment, (feats, pos), sep_tok, target, ans_type = bank.assemble(
+                    take[s:e], mode=mode if isinstance(mode, str) else list(mode[s:e]))
+                logits = self._encode_and_classify(cls_tok, input_txt, desc, segment, feats, pos, sep_tok, infer=path == "inference")
+                if path == "inference":
+                    ops.bce_fwd_bwd(logits, A, R=e - s, ld=self.Ap, arg_infer=pred[s:e])
+                else:
+                    ops.bce_fwd_bwd(logits, A, R=e - s, ld=self.Ap, target=target, ans_type=ans_type, stats=stats, arg_train=pred[s:e])
+            score, counters = ops.vqa_score(pred, dev_idx, bank.ans_ptr, bank.ans_label, bank.ans_score, bank.ans_type, group=bank.group)
+        # the one read-back: the integer counters and the bits of the f32 BCE sum
+        host = torch.cat([counters.reshape(-1), stats.view(torch.int32).to(torch.int64)]).cpu()
+        out = vqa_metrics(host[:counters.numel()].view(-1, 3, 2))
+        if path == "train":
+            k = counters.numel() + 1                      # stats[1]: the BCE sum
+            out["loss"] = float(host[k:k + 1].to(torch.int32).view(torch.float32)) / float(n * A)
+        out["pred"], out["score"] = pred, score
+        return out
 
     # ------------------------------------------------------------------ state dict (the reference's VQA layout)
     def state_dict(self, *a, **k):
