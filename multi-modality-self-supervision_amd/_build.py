@@ -41,7 +41,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, "mv_common.h"), os.path.join(CSRC, "mv_gemm_common.h"), os.path.join(CSRC, "mv_gemm_ring.h"), os.path.join(CSRC, "mv_gemm_group.h"), os.path.join(CSRC, "mv_gemm_plan.h"),
-               os.path.join(CSRC, "mv_dispatch.h"),
+               os.path.join(CSRC, "mv_dispatch.h"), os.path.join(CSRC, "mv_bank.h"),
                os.path.join(os.path.dirname(HERE), "include", "medvill.h")]
     dbg_header = os.path.join(os.path.dirname(HERE), "include", "medvill_debug.h")      # only the debug build of mv_api.hip includes it
     jobs = []

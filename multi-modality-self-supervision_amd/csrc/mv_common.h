@@ -232,23 +232,3 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 static inline int mv_dtype_size(int dt) { return dt == MV_F32 ? 4 : 2; }   // MV_BF16 and MV_F16 are both 2 bytes
-
-// One block's share of a row copy (the bank gathers of mv_pair_assemble / mv_report_assemble): bytes [lo, min(n, lo + chunk)) of s -> d
-// by the block's nt threads.  vec16: n, chunk and both bases are multiples of 16 -> 16 bytes per lane; else 2-byte units (every
-// encoding's size divides into them).
-__device__ __forceinline__ void mv_copy_chunk(const unsigned char* __restrict__ s, unsigned char* __restrict__ d, size_t n, size_t lo,
-                                              size_t chunk, int vec16, int nt) {
-  if (lo >= n) return;
-  const size_t hi = min(n, lo + chunk);
-  if (vec16) {
-    const uint4* s4 = (const uint4*)(s + lo);
-    uint4* d4 = (uint4*)(d + lo);
-    const size_t n4 = (hi - lo) >> 4;
-    for (size_t i = threadIdx.x; i < n4; i += nt) d4[i] = s4[i];
-  } else {
-    const uint16_t* s2 = (const uint16_t*)(s + lo);
-    uint16_t* d2 = (uint16_t*)(d + lo);
-    const size_t n2 = (hi - lo) >> 1;
-    for (size_t i = threadIdx.x; i < n2; i += nt) d2[i] = s2[i];
-  }
-}

@@ -10,11 +10,11 @@
 // THE DRAW.  random.shuffle of the candidates (data_loader.py:353-360) becomes "order the candidates by their 32-bit words": the rank of
 // text index t is the number of candidates t' with (word[t'], t') < (word[t], t), so equal words go to the lower index and the order is
 // a permutation for any words.  For independent uniform words that is a uniform shuffle up to the ties' 2^-32.
-#include "mv_common.h"
+#include "mv_bank.h"
 
 namespace {
+using namespace mv_bank;
 
-constexpr int NT = 256;
 constexpr int MAX_T = 1024;           // text ids per row (LDS: T + 1 words)
 constexpr int MAX_PRED = 64;          // prediction slots per sample
 constexpr int PLAN_MAX_B = 2048;
@@ -28,18 +28,18 @@ __global__ void report_draws_kernel(unsigned k0, unsigned k1, int n, uint32_t* _
 
 // ---------------------------------------------------------------------------------------------------- batch assembly
 // grid (B, chunks): every block of a sample copies one chunk of its feature row; chunk 0 also draws the masks and writes the text side.
+template <typename E>
 __global__ __launch_bounds__(NT) void report_assemble_kernel(
     const int64_t* __restrict__ txt_ids, const int32_t* __restrict__ txt_len, const int32_t* __restrict__ n_pred, int n_items,
-    const unsigned char* __restrict__ img, const int64_t* __restrict__ img_pos, const int32_t* __restrict__ idx,
-    const int32_t* __restrict__ family, int N, int T, int max_pred, unsigned k0, unsigned k1, const uint32_t* __restrict__ draws,
-    int64_t* __restrict__ input_txt, int64_t* __restrict__ segment, int32_t* __restrict__ desc, unsigned char* __restrict__ feats,
-    int64_t* __restrict__ pos_out, int64_t* __restrict__ masked_pos, int64_t* __restrict__ masked_lab, float* __restrict__ masked_w,
-    size_t row_bytes, size_t chunk_bytes, int vec16) {
+    const E* __restrict__ img, const int64_t* __restrict__ img_pos, const int32_t* __restrict__ idx, const int32_t* __restrict__ family,
+    int N, int T, int max_pred, unsigned k0, unsigned k1, const uint32_t* __restrict__ draws, int64_t* __restrict__ input_txt,
+    int64_t* __restrict__ segment, int32_t* __restrict__ desc, E* __restrict__ feats, int64_t* __restrict__ pos_out,
+    int64_t* __restrict__ masked_pos, int64_t* __restrict__ masked_lab, float* __restrict__ masked_w, ChunkPlan plan) {
   __shared__ uint32_t s_word[MAX_T + 1];
   __shared__ int s_sel[MAX_PRED];                 // text index per slot
   __shared__ unsigned char s_listed[MAX_T];
   const int i = blockIdx.x, tid = threadIdx.x;
-  const int d = min(max(idx[i], 0), n_items - 1);                   // (clamped: an index outside the bank reads no foreign memory)
+  const int d = clamp_item(idx[i], n_items);
   if (blockIdx.y == 0) {
     const int len = min(max(txt_len[d], 1), T);
     const int p = max(min(min(n_pred[d], max_pred), len), 0);
@@ -76,15 +76,10 @@ __global__ __launch_bounds__(NT) void report_assemble_kernel(
       input_txt[(size_t)i * T + t] = s_listed[t] ? TOK_MASK : src[t];
       segment[(size_t)i * T + t] = t < len ? 1 : 0;
     }
-    for (int j = tid; j < N; j += NT) pos_out[(size_t)i * N + j] = img_pos[(size_t)d * N + j];
-    if (tid == 0) {
-      desc[3 * i + 0] = family ? family[i] : FAMILY_S2S;
-      desc[3 * i + 1] = N + 2;
-      desc[3 * i + 2] = N + 2 + len;
-    }
+    copy_pos_row(img_pos, d, pos_out, i, N);
+    if (tid == 0) write_desc(desc, i, family ? family[i] : FAMILY_S2S, N, len);
   }
-  mv_copy_chunk(img + (size_t)d * row_bytes, feats + (size_t)i * row_bytes, row_bytes, (size_t)blockIdx.y * chunk_bytes, chunk_bytes,
-                vec16, NT);
+  copy_chunk(img + (size_t)d * plan.row, feats + (size_t)i * plan.row, plan.row, blockIdx.y * plan.chunk, plan.chunk, plan.vec);
 }
 
 // ---------------------------------------------------------------------------------------------------- row plan
@@ -224,21 +219,17 @@ extern "C" int mv_report_assemble(const int64_t* txt_ids, const int32_t* txt_len
   if (!mv_dtype_ok(dtype)) return MV_E_DTYPE;
   if (T > MAX_T || max_pred > MAX_PRED) return MV_E_SHAPE;
   if ((long long)N * F > 0x7fffffffLL || (long long)B * (T + 1) > 0x3fffffffLL) return MV_E_SHAPE;
-  const size_t row_bytes = (size_t)N * F * mv_dtype_size(dtype);
-  size_t chunk = 64 * 1024;
-  size_t chunks = (row_bytes + chunk - 1) / chunk;
-  if (chunks > 4096) {                                   // bound the grid's second dimension: larger chunks, still multiples of 16
-    chunk = ((row_bytes + 4095) / 4096 + 15) / 16 * 16;
-    chunks = (row_bytes + chunk - 1) / chunk;
-  }
-  const int vec16 = (row_bytes % 16 == 0 && ((uintptr_t)img_feats % 16) == 0 && ((uintptr_t)feats % 16) == 0) ? 1 : 0;
   unsigned k0, k1;
   mv_derive_keys(key, step, k0, k1);
-  report_assemble_kernel<<<dim3((unsigned)B, (unsigned)chunks), NT, 0, stream>>>(
-      txt_ids, txt_len, n_pred, n_items, (const unsigned char*)img_feats, img_pos, idx, family, N, T, max_pred, k0, k1, draws, input_txt,
-      segment, desc, (unsigned char*)feats, pos_out, masked_pos, masked_lm_labels, masked_weights, row_bytes, chunk, vec16);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  typedef mv_types<float, bf16_t, f16_t> Accept;      // f16 runs the bf16 instantiation: 2-byte elements move as bits (mv_bits_t)
+  return mv_with_type(dtype, Accept{}, [&](auto t) -> int {
+    typedef mv_bits_t<MV_T(t)> E;
+    const ChunkPlan p = chunk_plan((unsigned)((long long)N * F), sizeof(E), img_feats, feats);
+    hipLaunchKernelGGL(report_assemble_kernel<E>, dim3((unsigned)B, p.chunks), dim3(NT), 0, stream, txt_ids, txt_len, n_pred, n_items,
+                       (const E*)img_feats, img_pos, idx, family, N, T, max_pred, k0, k1, draws, input_txt, segment, desc, (E*)feats, pos_out,
+                       masked_pos, masked_lm_labels, masked_weights, p);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int mv_report_plan(const int64_t* pos, const int64_t* labels, const float* weights, const int32_t* valid_len, int B, int P, int L,

@@ -10,11 +10,11 @@
 // gives -- the reference's np.argsort(sim)[::-1]; numpy's default sort is stable for short arrays only, so beyond that the reference's
 // order among exact ties is unspecified and this rule is the definition.  (numpy itself would put a NaN FIRST after the reversal; a NaN
 // score is a broken candidate and is ranked last here.)
-#include "mv_common.h"
+#include "mv_bank.h"
 
 namespace {
+using namespace mv_bank;              // NT: every block of this file
 
-constexpr int NT = 256;
 constexpr int NW = NT / 64;
 constexpr int MAX_DRAWS = 300;        // the reference's `for itr in range(300)` (:119)
 constexpr int FAMILY_1D = 4;
@@ -68,34 +68,30 @@ __global__ void pair_negatives_kernel(const int32_t* __restrict__ idx, int B, in
 
 // ---------------------------------------------------------------------------------------------------- pair batches
 // grid (R, chunks): every block of a pair copies one chunk of its feature row; chunk 0 also writes the text side.
+template <typename E>
 __global__ __launch_bounds__(NT) void pair_assemble_kernel(const int64_t* __restrict__ txt_ids, const int32_t* __restrict__ txt_len,
-                                                           int T_items, const unsigned char* __restrict__ img, int I_items,
+                                                           int T_items, const E* __restrict__ img, int I_items,
                                                            const int64_t* __restrict__ img_pos, const int32_t* __restrict__ pairs, int N,
                                                            int S, int64_t* __restrict__ input_txt, int64_t* __restrict__ segment,
                                                            int32_t* __restrict__ n_ids, int32_t* __restrict__ desc,
-                                                           unsigned char* __restrict__ feats, int64_t* __restrict__ pos_out,
-                                                           size_t row_bytes, size_t chunk_bytes, int vec16) {
+                                                           E* __restrict__ feats, int64_t* __restrict__ pos_out, ChunkPlan plan) {
   const int r = blockIdx.x, T = S + 1;
-  const int im = min(max(pairs[2 * r], 0), I_items - 1);          // (clamped: an index outside its bank reads no foreign memory)
-  const int tx = min(max(pairs[2 * r + 1], 0), T_items - 1);
+  const int im = clamp_item(pairs[2 * r], I_items);
+  const int tx = clamp_item(pairs[2 * r + 1], T_items);
   if (blockIdx.y == 0) {
     const int64_t* src = txt_ids + (size_t)tx * T;
     for (int t = threadIdx.x; t < T; t += NT) {
       input_txt[(size_t)r * T + t] = src[t];
       segment[(size_t)r * T + t] = 1;                             // full_dset_retrieval.py:203: ones over all S + 1 positions
     }
-    if (img_pos)
-      for (int j = threadIdx.x; j < N; j += NT) pos_out[(size_t)r * N + j] = img_pos[(size_t)im * N + j];
+    copy_pos_row(img_pos, im, pos_out, r, N);
     if (threadIdx.x == 0) {
       const int len = min(max(txt_len[tx], 0), T);
       n_ids[r] = len;
-      desc[3 * r + 0] = FAMILY_1D;
-      desc[3 * r + 1] = N + 2;
-      desc[3 * r + 2] = N + 2 + len;
+      write_desc(desc, r, FAMILY_1D, N, len);
     }
   }
-  mv_copy_chunk(img + (size_t)im * row_bytes, feats + (size_t)r * row_bytes, row_bytes, (size_t)blockIdx.y * chunk_bytes, chunk_bytes,
-                vec16, NT);
+  copy_chunk(img + (size_t)im * plan.row, feats + (size_t)r * plan.row, plan.row, blockIdx.y * plan.chunk, plan.chunk, plan.vec);
 }
 
 // ---------------------------------------------------------------------------------------------------- ranking
@@ -239,19 +235,14 @@ extern "C" int mv_pair_assemble(const int64_t* txt_ids, const int32_t* txt_len, 
   if ((img_pos != nullptr) != (pos_out != nullptr)) return MV_E_ARG;
   if (!mv_dtype_ok(dtype)) return MV_E_DTYPE;
   if ((long long)N * F > 0x7fffffffLL || R > 0x3fffffff) return MV_E_SHAPE;
-  const size_t row_bytes = (size_t)N * F * mv_dtype_size(dtype);
-  size_t chunk = 64 * 1024;
-  size_t chunks = (row_bytes + chunk - 1) / chunk;
-  if (chunks > 4096) {                                   // bound the grid's second dimension: larger chunks, still multiples of 16
-    chunk = ((row_bytes + 4095) / 4096 + 15) / 16 * 16;
-    chunks = (row_bytes + chunk - 1) / chunk;
-  }
-  const int vec16 = (row_bytes % 16 == 0 && ((uintptr_t)img_feats % 16) == 0 && ((uintptr_t)feats % 16) == 0) ? 1 : 0;
-  pair_assemble_kernel<<<dim3((unsigned)R, (unsigned)chunks), NT, 0, stream>>>(
-      txt_ids, txt_len, T_items, (const unsigned char*)img_feats, I_items, img_pos, pairs, N, S, input_txt, segment, n_ids, desc,
-      (unsigned char*)feats, pos_out, row_bytes, chunk, vec16);
-  MV_CHECK_LAUNCH();
-  return MV_OK;
+  typedef mv_types<float, bf16_t, f16_t> Accept;      // f16 runs the bf16 instantiation: 2-byte elements move as bits (mv_bits_t)
+  return mv_with_type(dtype, Accept{}, [&](auto t) -> int {
+    typedef mv_bits_t<MV_T(t)> E;
+    const ChunkPlan p = chunk_plan((unsigned)((long long)N * F), sizeof(E), img_feats, feats);
+    hipLaunchKernelGGL(pair_assemble_kernel<E>, dim3((unsigned)R, p.chunks), dim3(NT), 0, stream, txt_ids, txt_len, T_items,
+                       (const E*)img_feats, I_items, img_pos, pairs, N, S, input_txt, segment, n_ids, desc, (E*)feats, pos_out, p);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int mv_rank_groups(const float* logits, const int32_t* labels, int G, int C, const int32_t* ks, int nk, float* p, int32_t* pos,

@@ -6,42 +6,14 @@
 //   mv_vqa_score     the score of a batch of predicted answer columns, and the integer sums of a whole evaluation by (group, type)
 // Integer and copy work.  mv_vqa_assemble accumulates nothing: the same input gives the same bits on every run.  mv_vqa_score adds
 // 32.32 fixed-point terms with 64-bit integer atomics, so its sums do not depend on the order in which samples finish either.
-#include "mv_dispatch.h"
+#include "mv_bank.h"
 
 namespace {
+using namespace mv_bank;
 
-constexpr int NT = 256;
 constexpr int MAX_T = 1024;           // text ids per row
 constexpr int MAX_G = 8;              // groups of mv_vqa_score
 constexpr int FAMILY_1D = 4;
-constexpr int VEC_BYTES = 16;         // one lane's load / store on the aligned path
-constexpr int UNROLL = 4;             // vectors a lane holds in flight
-constexpr int CHUNK_BYTES = 65536;    // one block's share of a feature row
-constexpr int MAX_CHUNKS = 1024;      // blocks per sample: longer rows take larger chunks
-
-// One block's share of a feature row: elements [lo, min(n, lo + chunk)) of s -> d.  vec: n, chunk and both bases are multiples of 16
-// bytes -> 16 bytes per lane, UNROLL loads issued before the first store; else element by element.
-template <typename T>
-__device__ __forceinline__ void copy_chunk(const T* __restrict__ s, T* __restrict__ d, unsigned n, unsigned lo, unsigned chunk, int vec) {
-  if (lo >= n) return;
-  const unsigned cnt = min(n - lo, chunk);
-  if (vec) {
-    const uint4* s4 = (const uint4*)(s + lo);
-    uint4* d4 = (uint4*)(d + lo);
-    const unsigned n4 = cnt / (VEC_BYTES / sizeof(T));
-    const unsigned body = n4 / (UNROLL * NT) * (UNROLL * NT);
-    for (unsigned i = threadIdx.x; i < body; i += UNROLL * NT) {
-      uint4 v[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) v[u] = s4[i + u * NT];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) d4[i + u * NT] = v[u];
-    }
-    for (unsigned i = body + threadIdx.x; i < n4; i += NT) d4[i] = s4[i];
-  } else {
-    for (unsigned i = threadIdx.x; i < cnt; i += NT) d[lo + i] = s[lo + i];
-  }
-}
 
 struct VqaBankArgs {                  // the bank, as mv_vqa_assemble reads it
   const int64_t* txt_ids;
@@ -61,11 +33,10 @@ __global__ __launch_bounds__(NT) void vqa_assemble_kernel(VqaBankArgs bk, const 
                                                           const int32_t* __restrict__ family, int N, int Tn, int A,
                                                           int64_t* __restrict__ input_txt, int64_t* __restrict__ segment,
                                                           int32_t* __restrict__ desc, T* __restrict__ feats, int64_t* __restrict__ pos_out,
-                                                          float* __restrict__ target, int32_t* __restrict__ ans_type_out,
-                                                          unsigned row_elems, unsigned chunk_elems, int vec) {
+                                                          float* __restrict__ target, int32_t* __restrict__ ans_type_out, ChunkPlan plan) {
   const int i = blockIdx.x, tid = threadIdx.x;
-  const int d = min(max(idx[i], 0), bk.n_questions - 1);            // (clamped: an index outside its bank reads no foreign memory)
-  const int m = min(max(bk.q_img[d], 0), bk.n_images - 1);
+  const int d = clamp_item(idx[i], bk.n_questions);
+  const int m = clamp_item(bk.q_img[d], bk.n_images);
   if (blockIdx.y == 0) {
     const int len = min(max(bk.txt_len[d], 1), Tn);
     const int64_t* src = bk.txt_ids + (size_t)d * Tn;
@@ -73,13 +44,11 @@ __global__ __launch_bounds__(NT) void vqa_assemble_kernel(VqaBankArgs bk, const 
       input_txt[(size_t)i * Tn + t] = src[t];                       // unmasked: VQA predicts no token (data_loader.py:378-381)
       segment[(size_t)i * Tn + t] = t < len ? 1 : 0;
     }
-    for (int j = tid; j < N; j += NT) pos_out[(size_t)i * N + j] = bk.img_pos[(size_t)m * N + j];
+    copy_pos_row(bk.img_pos, m, pos_out, i, N);
     float* trow = target + (size_t)i * A;
     for (int a = tid; a < A; a += NT) trow[a] = 0.f;
     if (tid == 0) {
-      desc[3 * i + 0] = family ? family[i] : FAMILY_1D;
-      desc[3 * i + 1] = N + 2;
-      desc[3 * i + 2] = N + 2 + len;
+      write_desc(desc, i, family ? family[i] : FAMILY_1D, N, len);
       ans_type_out[i] = bk.ans_type[d];
     }
     __syncthreads();                                                // (the block's own zeros are ordered before the entries below)
@@ -91,7 +60,7 @@ __global__ __launch_bounds__(NT) void vqa_assemble_kernel(VqaBankArgs bk, const 
       }
     }
   }
-  copy_chunk(img + (size_t)m * row_elems, feats + (size_t)i * row_elems, row_elems, blockIdx.y * chunk_elems, chunk_elems, vec);
+  copy_chunk(img + (size_t)m * plan.row, feats + (size_t)i * plan.row, plan.row, blockIdx.y * plan.chunk, plan.chunk, plan.vec);
 }
 
 // 32.32 fixed point of a score, rounded to nearest even (mv_rank_groups' device): integer sums do not depend on the order of the samples.
@@ -140,17 +109,9 @@ extern "C" int mv_vqa_assemble(const int64_t* txt_ids, const int32_t* txt_len, c
   const VqaBankArgs bk = {txt_ids, txt_len, q_img, ans_ptr, ans_label, ans_score, ans_type, img_pos, n_questions, n_images, nnz};
   return mv_with_type(dtype, Accept{}, [&](auto t) -> int {
     typedef mv_bits_t<MV_T(t)> E;
-    constexpr unsigned per_vec = VEC_BYTES / sizeof(E);
-    const unsigned row = (unsigned)((long long)N * F);
-    unsigned chunk = CHUNK_BYTES / sizeof(E);
-    unsigned chunks = (row + chunk - 1) / chunk;
-    if (chunks > MAX_CHUNKS) {                         // bound the grid's second dimension: larger chunks, still whole vectors
-      chunk = ((row + MAX_CHUNKS - 1) / MAX_CHUNKS + per_vec - 1) / per_vec * per_vec;
-      chunks = (row + chunk - 1) / chunk;
-    }
-    const int vec = (row % per_vec == 0 && ((uintptr_t)img_feats % VEC_BYTES) == 0 && ((uintptr_t)feats % VEC_BYTES) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(vqa_assemble_kernel<E>, dim3((unsigned)B, chunks), dim3(NT), 0, stream, bk, (const E*)img_feats, idx, family, N, T, A,
-                       input_txt, segment, desc, (E*)feats, pos_out, target, ans_type_out, row, chunk, vec);
+    const ChunkPlan p = chunk_plan((unsigned)((long long)N * F), sizeof(E), img_feats, feats);
+    hipLaunchKernelGGL(vqa_assemble_kernel<E>, dim3((unsigned)B, p.chunks), dim3(NT), 0, stream, bk, (const E*)img_feats, idx, family, N, T,
+                       A, input_txt, segment, desc, (E*)feats, pos_out, target, ans_type_out, p);
     return (int)hipGetLastError();
   });
 }

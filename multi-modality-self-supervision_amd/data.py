@@ -275,7 +275,7 @@ def seq2seq_finetune_batch(ids, lengths, n_regions: int, max_len: int, max_pred:
                 masked_pos=pos, masked_lm_labels=lab, masked_weights=w, n_ids=n_ids)
 
 
-# ---------------------------------------------------------------------------------------------------- retrieval banks
+# ---------------------------------------------------------------------------------------------------- device-resident banks
 def check_pairs(pairs, n_images: int, n_texts: int) -> torch.Tensor:
     """Host-side check of a pair list given on the host: -> int32 [R, 2] (image item, text item), every index inside its bank."""
     p = torch.as_tensor(pairs)
@@ -289,21 +289,17 @@ def check_pairs(pairs, n_images: int, n_texts: int) -> torch.Tensor:
     return p.to(torch.int32).contiguous()
 
 
-class RetrievalBank:
-    """The two sides of a retrieval data set, resident on the device (Downstream_task/Retrieval/full_dset_retrieval.py builds every pair
-    on the host, and pushes an image through the region encoder once per pair it appears in):
-      add_texts(ids, lengths)   ids int64 [n, S+1], each row tokens + [SEP] + [PAD]... as data_processing (:183-198) lays it out;
-                                lengths [n] count the [SEP]
+class DeviceBank:
+    """What the device-resident banks share: a text side and an image side filled once, and the host half of a batch -- the index
+    list, the mask family per sample and the descriptors' host copy -- so that no batch reads anything back.
+      add_texts(ids, lengths)   ids int64 [n, S+1], each row tokens + [SEP] + [PAD]... as data_processing
+                                (Downstream_task/Retrieval/full_dset_retrieval.py:183-198) lays it out; lengths [n] count the [SEP]
       add_images(input_img)     whatever CXRBERT.forward accepts as input_img -- (region features [n, N, F], positions [n, N]) or pixels for
                                 the model's region encoder -- run ONCE per distinct image; the features are stored in the engine's input
                                 encoding
-      assemble(pairs)           (image item, text item) index pairs -> the arguments of CXRBertForRetrieval.forward, with `attn_mask` a
-                                MaskDesc of the 1-D family (one mv_pair_assemble launch).  Pairs given on the host are checked against the
-                                banks there and the descriptors' host copy is built from the lengths' host copy (no read-back); pairs that
-                                live on the device are clamped into the banks by the kernel.
-    `model`: a CXRBertForRetrieval / CXRBERT (its engine gives device and encoding); None with device= / feat_dtype= for host-only use."""
+    `model`: a task model or a CXRBERT (its engine gives device and encoding); None with device= / feat_dtype= for host-only use."""
 
-    def __init__(self, model=None, device=None, feat_dtype=None, class_id=None):
+    def __init__(self, model=None, device=None, feat_dtype=None):
         bert = getattr(model, "bert", model)
         self.bert = bert
         if bert is not None:
@@ -314,10 +310,7 @@ class RetrievalBank:
         self.feat_dtype = feat_dtype if feat_dtype is not None else torch.float32
         self.txt_ids = self.txt_len = self.img_feats = self.img_pos = None
         self._len_host = None
-        self.class_id = None
         self._tok = {}
-        if class_id is not None:
-            self.set_classes(class_id)
 
     @property
     def n_texts(self):
@@ -359,11 +352,6 @@ class RetrievalBank:
         self.img_pos = pos if self.img_pos is None else torch.cat([self.img_pos, pos])
         return self
 
-    def set_classes(self, class_id):
-        """int [n]: the class of item i for the sampler's label_conditioned mode (None: plain sampling)."""
-        self.class_id = None if class_id is None else torch.as_tensor(class_id).to(torch.int32).reshape(-1).to(self.device).contiguous()
-        return self
-
     def _tokens(self, R):
         t = self._tok.get(R)
         if t is None:
@@ -371,13 +359,74 @@ class RetrievalBank:
                                 torch.full((R, 1), SEP, dtype=torch.int64, device=self.device))
         return t
 
+    @staticmethod
+    def _index_list(idx, bound: int, noun: str) -> torch.Tensor:
+        """An index list given on the host, checked against the bank of `bound` `noun`: -> int64 [B]."""
+        h = torch.as_tensor(idx).reshape(-1)
+        if h.numel() == 0 or h.dtype.is_floating_point or h.dtype == torch.bool:
+            raise ValueError(f"idx must be a non-empty integer list of {noun}")
+        h = h.to(torch.int64)
+        if int(h.min()) < 0 or int(h.max()) >= bound:
+            raise IndexError(f"idx outside the bank of {bound} {noun}")
+        return h
+
+    def _indices(self, idx, bound: int, noun: str):
+        """A batch's index list -> (int32 [B] on the device, int64 [B] on the host or None).  A device tensor is taken as it is (the
+        kernel clamps it into the bank); anything else passes _index_list."""
+        if torch.is_tensor(idx) and idx.device.type != "cpu":
+            if idx.dtype != torch.int32 or idx.dim() != 1:
+                raise TypeError("idx on the device: int32 [B]")
+            return idx.contiguous(), None
+        h = self._index_list(idx, bound, noun)
+        return h.to(torch.int32).to(self.device), h
+
+    @staticmethod
+    def _families(mode, B: int) -> torch.Tensor:
+        """mode "s2s" / "bi" / "bar", or one per sample -> the mask family of each sample, int32 [B] on the host."""
+        modes = [mode] * B if isinstance(mode, str) else list(mode)
+        if len(modes) != B or any(m not in _S2S_FAMILY for m in modes):
+            raise ValueError(f"mode: one of {sorted(_S2S_FAMILY)}, or one per sample ({B})")
+        return torch.tensor([FAMILY_ID[_S2S_FAMILY[m]] for m in modes], dtype=torch.int32)
+
+    def host_descriptors(self, text_items, family):
+        """int32 [B, 3] = {family, N+2, N+2+len}: what an assemble kernel writes, from the host copy of the lengths.  text_items int64 [B]
+        on the host; family: one id, or int32 [B]."""
+        N = int(self.img_feats.shape[1])
+        d = torch.empty((text_items.numel(), 3), dtype=torch.int32)
+        d[:, 0], d[:, 1], d[:, 2] = family, N + 2, N + 2 + self._len_host.index_select(0, text_items)
+        return d
+
+    def _batch(self, out, host_desc):
+        """The six arguments every task's forward starts with, from an assemble kernel's outputs: (cls_tok, input_txt, attn_mask,
+        segment, input_img, sep_tok), attn_mask a MaskDesc, input_img = (features, positions)."""
+        B, (N, T) = int(out["desc"].shape[0]), (int(self.img_feats.shape[1]), int(self.txt_ids.shape[1]))
+        cls_tok, sep_tok = self._tokens(B)
+        return cls_tok, out["input_txt"], MaskDesc(out["desc"], T + N + 2, host=host_desc), out["segment"], (out["feats"], out["pos"]), sep_tok
+
+
+# ---------------------------------------------------------------------------------------------------- retrieval banks
+class RetrievalBank(DeviceBank):
+    """The two sides of a retrieval data set, resident on the device (Downstream_task/Retrieval/full_dset_retrieval.py builds every pair
+    on the host, and pushes an image through the region encoder once per pair it appears in):
+      add_texts, add_images     DeviceBank's
+      set_classes(class_id)     the class of every item, for the sampler's label_conditioned mode
+      assemble(pairs)           (image item, text item) index pairs -> the arguments of CXRBertForRetrieval.forward, with `attn_mask` a
+                                MaskDesc of the 1-D family (one mv_pair_assemble launch).  Pairs given on the host are checked against the
+                                banks there and the descriptors' host copy is built from the lengths' host copy (no read-back); pairs that
+                                live on the device are clamped into the banks by the kernel."""
+
+    def __init__(self, model=None, device=None, feat_dtype=None, class_id=None):
+        super().__init__(model, device, feat_dtype)
+        self.set_classes(class_id)
+
+    def set_classes(self, class_id):
+        """int [n]: the class of item i for the sampler's label_conditioned mode (None: plain sampling)."""
+        self.class_id = None if class_id is None else torch.as_tensor(class_id).to(torch.int32).reshape(-1).to(self.device).contiguous()
+        return self
+
     def host_descriptors(self, pairs_host):
         """int32 [R, 3] = {FAMILY_ID['1d'], N+2, N+2+len}: what mv_pair_assemble writes, from the host copy of the lengths."""
-        N = int(self.img_feats.shape[1])
-        ln = self._len_host.index_select(0, pairs_host[:, 1].to(torch.int64))
-        d = torch.empty((pairs_host.shape[0], 3), dtype=torch.int32)
-        d[:, 0], d[:, 1], d[:, 2] = FAMILY_ID["1d"], N + 2, N + 2 + ln
-        return d
+        return super().host_descriptors(pairs_host[:, 1].to(torch.int64), FAMILY_ID["1d"])
 
     def assemble(self, pairs):
         """-> (cls_tok, input_txt, attn_mask, segment, input_img, sep_tok), attn_mask a MaskDesc, input_img = (features, positions)."""
@@ -393,22 +442,18 @@ class RetrievalBank:
             hp = check_pairs(pairs, self.n_images, self.n_texts)
             host = self.host_descriptors(hp)
             dev_pairs = hp.to(self.device)
-        out = ops.pair_assemble(self.txt_ids, self.txt_len, self.img_feats, self.img_pos, dev_pairs)
-        R, N, T = int(dev_pairs.shape[0]), int(self.img_feats.shape[1]), int(self.txt_ids.shape[1])
-        cls_tok, sep_tok = self._tokens(R)
-        desc = MaskDesc(out["desc"], T + N + 2, host=host)
-        return cls_tok, out["input_txt"], desc, out["segment"], (out["feats"], out["pos"]), sep_tok
+        return self._batch(ops.pair_assemble(self.txt_ids, self.txt_len, self.img_feats, self.img_pos, dev_pairs), host)
 
 
 # ---------------------------------------------------------------------------------------------------- report bank
-class ReportBank(RetrievalBank):
+class ReportBank(DeviceBank):
     """A report-generation data set resident on the device, item i = (image i, report i): what seq2seq_finetune_batch builds per sample on
     the host (Preprocess4Seq2seq, Downstream_task/report_generation_and_vqa/sc/data_loader.py:330-419) comes out of one
     mv_report_assemble launch per batch, and an image passes the region encoder once, not once per epoch.
-      add_reports(ids, lengths)  ids int64 [n, T], each row tokens + [SEP] + [PAD]... (RetrievalBank.add_texts' layout); lengths [n] count
+      add_reports(ids, lengths)  ids int64 [n, T], each row tokens + [SEP] + [PAD]... (DeviceBank.add_texts' layout); lengths [n] count
                                  the [SEP].  Also fixes n_pred = min(max_pred, max(1, int(round((len - 1) * mask_prob)))) per item, with
                                  Python's round as in the reference (1.5 -> 2, 4.5 -> 4), from the host copy of the lengths.
-      add_images(input_img)      as RetrievalBank.add_images
+      add_images(input_img)      as DeviceBank.add_images
       assemble(idx, mode, ...)   -> (cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, lists): the arguments of
                                  CXRBertForReportFinetune.forward and lists = dict(masked_lm_labels, masked_pos, masked_weights) on the
                                  device.  mode "s2s" / "bi" / "bar" (data_loader.py:395-412) or one per sample -- the reference draws the
@@ -439,34 +484,12 @@ class ReportBank(RetrievalBank):
             raise ValueError("ReportBank.assemble: the bank is empty (add_reports, add_images)")
         if n != self.n_images or self.n_pred is None or int(self.n_pred.numel()) != n:
             raise ValueError(f"ReportBank.assemble: {n} reports (add_reports) and {self.n_images} images: item i is image i with report i")
-        host_idx = None
-        if torch.is_tensor(idx) and idx.device.type != "cpu":
-            if idx.dtype != torch.int32 or idx.dim() != 1:
-                raise TypeError("idx on the device: int32 [B]")
-            dev_idx = idx.contiguous()
-        else:
-            host_idx = torch.as_tensor(idx).reshape(-1)
-            if host_idx.numel() == 0 or host_idx.dtype.is_floating_point or host_idx.dtype == torch.bool:
-                raise ValueError("idx must be a non-empty integer list of bank items")
-            host_idx = host_idx.to(torch.int64)
-            if int(host_idx.min()) < 0 or int(host_idx.max()) >= n:
-                raise IndexError(f"idx outside the bank of {n} items")
-            dev_idx = host_idx.to(torch.int32).to(self.device)
-        B = int(dev_idx.numel())
-        modes = [mode] * B if isinstance(mode, str) else list(mode)
-        if len(modes) != B or any(m not in _S2S_FAMILY for m in modes):
-            raise ValueError(f"mode: one of {sorted(_S2S_FAMILY)}, or one per sample ({B})")
-        fam_host = torch.tensor([FAMILY_ID[_S2S_FAMILY[m]] for m in modes], dtype=torch.int32)
-        N, T = int(self.img_feats.shape[1]), int(self.txt_ids.shape[1])
-        host = None
-        if host_idx is not None:
-            host = torch.empty((B, 3), dtype=torch.int32)
-            host[:, 0], host[:, 1], host[:, 2] = fam_host, N + 2, N + 2 + self._len_host.index_select(0, host_idx)
+        dev_idx, host_idx = self._indices(idx, n, "items")
+        fam_host = self._families(mode, int(dev_idx.numel()))
+        host = None if host_idx is None else self.host_descriptors(host_idx, fam_host)
         out = ops.report_assemble(self.txt_ids, self.txt_len, self.n_pred, self.img_feats, self.img_pos, dev_idx, self.max_pred,
                                   family=fam_host.to(self.device), key=key, step=step, draws=draws)
-        cls_tok, sep_tok = self._tokens(B)
-        lists = {k: out[k] for k in ("masked_lm_labels", "masked_pos", "masked_weights")}
-        return cls_tok, out["input_txt"], MaskDesc(out["desc"], T + N + 2, host=host), out["segment"], (out["feats"], out["pos"]), sep_tok, lists
+        return self._batch(out, host) + ({k: out[k] for k in ("masked_lm_labels", "masked_pos", "masked_weights")},)
 
 
 # ---------------------------------------------------------------------------------------------------- VQA bank
@@ -488,11 +511,11 @@ def vqa_answer_type(t) -> int:
     return v if v in (0, 1) and v == t else 2
 
 
-class VqaBank(RetrievalBank):
+class VqaBank(DeviceBank):
     """A VQA data set resident on the device: question i = (image q_img[i], question i, its sparse soft answers, its answer type, its
     group).  Many questions share one image (VQA-RAD: 315 images for 3,064 training questions, data_loader.py:236-273), so an image
     passes the region encoder once, not once per question, and a batch comes out of one mv_vqa_assemble launch.
-      add_images(input_img)   as RetrievalBank.add_images, once per distinct image
+      add_images(input_img)   as DeviceBank.add_images, once per distinct image
       add_questions(ids, lengths, image_item, labels, scores, ans_type, group=None)
                               ids int64 [n, T] / lengths [n]: add_texts' layout (tokens + [SEP] + [PAD]..., lengths count the [SEP]);
                               image_item int [n]: the item of the image bank; labels[i] / scores[i]: the answer['labels'] /
@@ -590,43 +613,21 @@ class VqaBank(RetrievalBank):
     def host_idx(self, idx):
         """A host index list, checked against both banks: -> int64 [B]."""
         self._check_filled()
-        h = torch.as_tensor(idx).reshape(-1)
-        if h.numel() == 0 or h.dtype.is_floating_point or h.dtype == torch.bool:
-            raise ValueError("idx must be a non-empty integer list of questions")
-        h = h.to(torch.int64)
-        if int(h.min()) < 0 or int(h.max()) >= self.n_questions:
-            raise IndexError(f"idx outside the bank of {self.n_questions} questions")
-        if int(self._q_img_host.index_select(0, h).max()) >= self.n_images:
-            raise ValueError(f"a listed question names an image outside the image bank of {self.n_images}")
-        return h
+        return self._check_images(self._index_list(idx, self.n_questions, "questions"))
 
-    def host_descriptors(self, host_idx, fam_host):
-        """int32 [B, 3] = {family, N+2, N+2+len}: what mv_vqa_assemble writes, from the host copy of the lengths."""
-        N = int(self.img_feats.shape[1])
-        d = torch.empty((host_idx.numel(), 3), dtype=torch.int32)
-        d[:, 0], d[:, 1], d[:, 2] = fam_host, N + 2, N + 2 + self._len_host.index_select(0, host_idx)
-        return d
+    def _check_images(self, host_idx):
+        if int(self._q_img_host.index_select(0, host_idx).max()) >= self.n_images:
+            raise ValueError(f"a listed question names an image outside the image bank of {self.n_images}")
+        return host_idx
 
     def assemble(self, idx, mode="bi"):
         from . import hip_ops as ops
-        host_idx = None
-        if torch.is_tensor(idx) and idx.device.type != "cpu":
-            self._check_filled()
-            if idx.dtype != torch.int32 or idx.dim() != 1:
-                raise TypeError("idx on the device: int32 [B]")
-            dev_idx = idx.contiguous()
-        else:
-            host_idx = self.host_idx(idx)
-            dev_idx = host_idx.to(torch.int32).to(self.device)
-        B = int(dev_idx.numel())
-        modes = [mode] * B if isinstance(mode, str) else list(mode)
-        if len(modes) != B or any(m not in _S2S_FAMILY for m in modes):
-            raise ValueError(f"mode: one of {sorted(_S2S_FAMILY)}, or one per sample ({B})")
-        fam_host = torch.tensor([FAMILY_ID[_S2S_FAMILY[m]] for m in modes], dtype=torch.int32)
+        self._check_filled()
+        dev_idx, host_idx = self._indices(idx, self.n_questions, "questions")
+        if host_idx is not None:
+            self._check_images(host_idx)
+        fam_host = self._families(mode, int(dev_idx.numel()))
         host = None if host_idx is None else self.host_descriptors(host_idx, fam_host)
         out = ops.vqa_assemble(self.txt_ids, self.txt_len, self.q_img, self.ans_ptr, self.ans_label, self.ans_score, self.ans_type,
                                self.img_feats, self.img_pos, dev_idx, self.n_answers, family=fam_host.to(self.device))
-        N, T = int(self.img_feats.shape[1]), int(self.txt_ids.shape[1])
-        cls_tok, sep_tok = self._tokens(B)
-        return (cls_tok, out["input_txt"], MaskDesc(out["desc"], T + N + 2, host=host), out["segment"], (out["feats"], out["pos"]), sep_tok,
-                out["target"], out["ans_type"])
+        return self._batch(out, host) + (out["target"], out["ans_type"])

@@ -905,28 +905,46 @@ def pair_negatives(idx, n, key=0, step=0, class_id=None, draws=None):
     return pairs, labels
 
 
+def _bank_check(who, txt_ids, txt_len, img_feats, img_pos, idx, family=None, per_text=(), pairs=False):
+    """What the three *_assemble wrappers check alike: -> (text rows, T, images, N, F, samples).  idx: the int32 index list [B], or
+    (pairs) the [R, 2] (image item, text item) list; per_text: further int32 tensors with one entry per text row; img_pos: None where
+    the caller allows a bank without positions.  (These run once per batch next to a 25 us kernel: plain loops, no generators.)"""
+    i32 = (txt_len, idx, *per_text) if family is None else (txt_len, idx, family, *per_text)
+    L.require_cuda(txt_ids, img_feats, img_pos, *i32)
+    if txt_ids.dtype != torch.int64 or (img_pos is not None and img_pos.dtype != torch.int64) or [t for t in i32 if t.dtype != torch.int32]:
+        raise TypeError(f"{who}: txt_ids / img_pos int64, every length, index and family tensor int32")
+    if txt_ids.dim() != 2 or img_feats.dim() != 3 or idx.dim() != (2 if pairs else 1) or (pairs and idx.shape[1] != 2):
+        raise ValueError(f"{who}: txt_ids [text rows, T], img_feats [images, N, F], {'pairs [R, 2]' if pairs else 'idx [B]'}")
+    n, T = txt_ids.shape
+    n_img, N, F = img_feats.shape
+    B = idx.shape[0]
+    if txt_len.shape != (n,) or [t for t in per_text if t.shape != (n,)] or (img_pos is not None and img_pos.shape != (n_img, N)) \
+            or (family is not None and family.shape != (B,)):
+        raise ValueError(f"{who}: one entry per text row, one position row per image, one family per sample")
+    if not (txt_ids.is_contiguous() and img_feats.is_contiguous() and (img_pos is None or img_pos.is_contiguous())) \
+            or [t for t in i32 if not t.is_contiguous()]:
+        raise ValueError(f"{who}: contiguous tensors")
+    return n, T, n_img, N, F, B
+
+
+def _bank_outputs(B, T, N, F, img_feats, pos=True):
+    """The outputs every assemble kernel writes; the caller adds its own."""
+    dev = img_feats.device
+    return dict(input_txt=torch.empty((B, T), dtype=torch.int64, device=dev), segment=torch.empty((B, T), dtype=torch.int64, device=dev),
+                desc=torch.empty((B, 3), dtype=torch.int32, device=dev), feats=torch.empty((B, N, F), dtype=img_feats.dtype, device=dev),
+                pos=torch.empty((B, N), dtype=torch.int64, device=dev) if pos else None)
+
+
 def pair_assemble(txt_ids, txt_len, img_feats, img_pos, pairs):
     """Pair batches from the banks (see mv_pair_assemble): -> dict(input_txt, segment, n_ids, desc, feats, pos)."""
-    L.require_cuda(txt_ids, txt_len, img_feats, img_pos, pairs)
-    if txt_ids.dtype != torch.int64 or txt_len.dtype != torch.int32 or pairs.dtype != torch.int32 or (img_pos is not None and img_pos.dtype != torch.int64):
-        raise TypeError("pair_assemble: txt_ids int64, txt_len int32, pairs int32, img_pos int64")
-    if txt_ids.dim() != 2 or img_feats.dim() != 3 or pairs.dim() != 2 or pairs.shape[1] != 2 or tuple(txt_len.shape) != (txt_ids.shape[0],):
-        raise ValueError("pair_assemble: txt_ids [T_items, S+1], txt_len [T_items], img_feats [I_items, N, F], pairs [R, 2]")
-    if not (txt_ids.is_contiguous() and img_feats.is_contiguous() and pairs.is_contiguous() and txt_len.is_contiguous()):
-        raise ValueError("pair_assemble: contiguous tensors")
-    Ti, T = txt_ids.shape
-    Ii, N, F = img_feats.shape
-    if img_pos is not None and (tuple(img_pos.shape) != (Ii, N) or not img_pos.is_contiguous()):
-        raise ValueError("pair_assemble: img_pos [I_items, N]")
-    R, dev = int(pairs.shape[0]), txt_ids.device
-    out = dict(input_txt=torch.empty((R, T), dtype=torch.int64, device=dev), segment=torch.empty((R, T), dtype=torch.int64, device=dev),
-               n_ids=torch.empty((R,), dtype=torch.int32, device=dev), desc=torch.empty((R, 3), dtype=torch.int32, device=dev),
-               feats=torch.empty((R, N, F), dtype=img_feats.dtype, device=dev),
-               pos=None if img_pos is None else torch.empty((R, N), dtype=torch.int64, device=dev))
-    rc = _lib().mv_pair_assemble(L.ptr(txt_ids), L.ptr(txt_len), int(Ti), L.ptr(img_feats), L.dt_of(img_feats), int(Ii), L.ptr(img_pos),
-                                 L.ptr(pairs), R, int(N), int(T) - 1, int(F), L.ptr(out["input_txt"]), L.ptr(out["segment"]),
+    Ti, T, Ii, N, F, R = _bank_check("pair_assemble", txt_ids, txt_len, img_feats, img_pos, pairs, pairs=True)
+    out = _bank_outputs(R, T, N, F, img_feats, pos=img_pos is not None)
+    out["n_ids"] = torch.empty((R,), dtype=torch.int32, device=pairs.device)
+    rc = _lib().mv_pair_assemble(L.ptr(txt_ids), L.ptr(txt_len), Ti, L.ptr(img_feats), L.dt_of(img_feats), Ii, L.ptr(img_pos),
+                                 L.ptr(pairs), R, N, T - 1, F, L.ptr(out["input_txt"]), L.ptr(out["segment"]),
                                  L.ptr(out["n_ids"]), L.ptr(out["desc"]), L.ptr(out["feats"]), L.ptr(out["pos"]), L.stream_ptr())
-    L.check(rc, f"mv_pair_assemble(R={R},N={N},S={T - 1},F={F})")
+    if rc:
+        L.check(rc, f"mv_pair_assemble(R={R},N={N},S={T - 1},F={F})")
     return out
 
 
@@ -969,37 +987,25 @@ def report_draws(key, step, B, T, device):
 def report_assemble(txt_ids, txt_len, n_pred, img_feats, img_pos, idx, max_pred, family=None, key=0, step=0, draws=None):
     """Report fine-tuning batches from the banks (see mv_report_assemble): -> dict(input_txt, segment, desc, feats, pos, masked_pos,
     masked_lm_labels, masked_weights).  draws: integers in [0, 2^32), [B, T+1], replacing the hash-generated words."""
-    L.require_cuda(txt_ids, txt_len, n_pred, img_feats, img_pos, idx, family)
-    if txt_ids.dtype != torch.int64 or txt_len.dtype != torch.int32 or n_pred.dtype != torch.int32 or img_pos.dtype != torch.int64 \
-            or idx.dtype != torch.int32 or (family is not None and family.dtype != torch.int32):
-        raise TypeError("report_assemble: txt_ids / img_pos int64, txt_len / n_pred / idx / family int32")
-    if txt_ids.dim() != 2 or img_feats.dim() != 3 or idx.dim() != 1:
-        raise ValueError("report_assemble: txt_ids [n_items, T], img_feats [n_items, N, F], idx [B]")
-    n, T = (int(s) for s in txt_ids.shape)
-    _, N, F = (int(s) for s in img_feats.shape)
-    B, dev = int(idx.numel()), txt_ids.device
-    if tuple(txt_len.shape) != (n,) or tuple(n_pred.shape) != (n,) or int(img_feats.shape[0]) != n or tuple(img_pos.shape) != (n, N) \
-            or (family is not None and tuple(family.shape) != (B,)):
-        raise ValueError("report_assemble: one length, prediction count, image and position row per item; one family per sample")
-    if not all(t.is_contiguous() for t in (txt_ids, txt_len, n_pred, img_feats, img_pos, idx) + (() if family is None else (family,))):
-        raise ValueError("report_assemble: contiguous tensors")
+    n, T, n_img, N, F, B = _bank_check("report_assemble", txt_ids, txt_len, img_feats, img_pos, idx, family, per_text=(n_pred,))
+    if n_img != n:
+        raise ValueError("report_assemble: one image per item")
     d32 = None
     if draws is not None:
-        d32 = _words_to_i32(draws).to(dev).contiguous()
+        d32 = _words_to_i32(draws).to(txt_ids.device).contiguous()
         if tuple(d32.shape) != (B, T + 1):
             raise ValueError(f"report_assemble: draws [B, T+1] = [{B}, {T + 1}]")
     P = int(max_pred)
-    out = dict(input_txt=torch.empty((B, T), dtype=torch.int64, device=dev), segment=torch.empty((B, T), dtype=torch.int64, device=dev),
-               desc=torch.empty((B, 3), dtype=torch.int32, device=dev), feats=torch.empty((B, N, F), dtype=img_feats.dtype, device=dev),
-               pos=torch.empty((B, N), dtype=torch.int64, device=dev), masked_pos=torch.empty((B, P), dtype=torch.int64, device=dev),
-               masked_lm_labels=torch.empty((B, P), dtype=torch.int64, device=dev),
-               masked_weights=torch.empty((B, P), dtype=torch.float32, device=dev))
+    out = _bank_outputs(B, T, N, F, img_feats)
+    for k, dt in (("masked_pos", torch.int64), ("masked_lm_labels", torch.int64), ("masked_weights", torch.float32)):
+        out[k] = torch.empty((B, P), dtype=dt, device=idx.device)
     rc = _lib().mv_report_assemble(L.ptr(txt_ids), L.ptr(txt_len), L.ptr(n_pred), n, L.ptr(img_feats), L.dt_of(img_feats), L.ptr(img_pos),
                                    L.ptr(idx), L.ptr(family), B, N, T, F, P, int(key) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF,
                                    L.ptr(d32), L.ptr(out["input_txt"]), L.ptr(out["segment"]), L.ptr(out["desc"]), L.ptr(out["feats"]),
                                    L.ptr(out["pos"]), L.ptr(out["masked_pos"]), L.ptr(out["masked_lm_labels"]),
                                    L.ptr(out["masked_weights"]), L.stream_ptr())
-    L.check(rc, f"mv_report_assemble(B={B},N={N},T={T},F={F},max_pred={P})")
+    if rc:
+        L.check(rc, f"mv_report_assemble(B={B},N={N},T={T},F={F},max_pred={P})")
     return out
 
 
@@ -1046,30 +1052,18 @@ def _vqa_csr_check(who, n, ans_ptr, ans_label, ans_score, ans_type):
 
 def vqa_assemble(txt_ids, txt_len, q_img, ans_ptr, ans_label, ans_score, ans_type, img_feats, img_pos, idx, n_answers, family=None):
     """VQA batches from the question bank (see mv_vqa_assemble): -> dict(input_txt, segment, desc, feats, pos, target, ans_type)."""
-    L.require_cuda(txt_ids, txt_len, q_img, ans_ptr, ans_label, ans_score, ans_type, img_feats, img_pos, idx, family)
-    if txt_ids.dtype != torch.int64 or txt_len.dtype != torch.int32 or q_img.dtype != torch.int32 or img_pos.dtype != torch.int64 \
-            or idx.dtype != torch.int32 or (family is not None and family.dtype != torch.int32):
-        raise TypeError("vqa_assemble: txt_ids / img_pos int64, txt_len / q_img / idx / family int32")
-    if txt_ids.dim() != 2 or img_feats.dim() != 3 or idx.dim() != 1:
-        raise ValueError("vqa_assemble: txt_ids [n_questions, T], img_feats [n_images, N, F], idx [B]")
-    n, T = (int(s) for s in txt_ids.shape)
-    n_img, N, F = (int(s) for s in img_feats.shape)
-    B, A, dev = int(idx.numel()), int(n_answers), txt_ids.device
-    nnz = _vqa_csr_check("vqa_assemble", n, ans_ptr, ans_label, ans_score, ans_type)
-    if tuple(txt_len.shape) != (n,) or tuple(q_img.shape) != (n,) or tuple(img_pos.shape) != (n_img, N) \
-            or (family is not None and tuple(family.shape) != (B,)):
-        raise ValueError("vqa_assemble: one length and image per question, one position row per image, one family per sample")
-    if not all(t.is_contiguous() for t in (txt_ids, txt_len, q_img, img_feats, img_pos, idx) + (() if family is None else (family,))):
-        raise ValueError("vqa_assemble: contiguous tensors")
-    out = dict(input_txt=torch.empty((B, T), dtype=torch.int64, device=dev), segment=torch.empty((B, T), dtype=torch.int64, device=dev),
-               desc=torch.empty((B, 3), dtype=torch.int32, device=dev), feats=torch.empty((B, N, F), dtype=img_feats.dtype, device=dev),
-               pos=torch.empty((B, N), dtype=torch.int64, device=dev), target=torch.empty((B, A), dtype=torch.float32, device=dev),
-               ans_type=torch.empty((B,), dtype=torch.int32, device=dev))
+    L.require_cuda(ans_ptr, ans_label, ans_score, ans_type)
+    n, T, n_img, N, F, B = _bank_check("vqa_assemble", txt_ids, txt_len, img_feats, img_pos, idx, family, per_text=(q_img,))
+    nnz, A = _vqa_csr_check("vqa_assemble", n, ans_ptr, ans_label, ans_score, ans_type), int(n_answers)
+    out = _bank_outputs(B, T, N, F, img_feats)
+    out["target"] = torch.empty((B, A), dtype=torch.float32, device=idx.device)
+    out["ans_type"] = torch.empty((B,), dtype=torch.int32, device=idx.device)
     rc = _lib().mv_vqa_assemble(L.ptr(txt_ids), L.ptr(txt_len), L.ptr(q_img), n, L.ptr(ans_ptr), L.ptr(ans_label) or None,
                                 L.ptr(ans_score) or None, nnz, L.ptr(ans_type), L.ptr(img_feats), L.dt_of(img_feats), L.ptr(img_pos), n_img,
                                 L.ptr(idx), L.ptr(family), B, N, T, F, A, L.ptr(out["input_txt"]), L.ptr(out["segment"]), L.ptr(out["desc"]),
                                 L.ptr(out["feats"]), L.ptr(out["pos"]), L.ptr(out["target"]), L.ptr(out["ans_type"]), L.stream_ptr())
-    L.check(rc, f"mv_vqa_assemble(B={B},N={N},T={T},F={F},A={A})")
+    if rc:
+        L.check(rc, f"mv_vqa_assemble(B={B},N={N},T={T},F={F},A={A})")
     return out
 
 

@@ -5,7 +5,8 @@
   fine-tuning, steps/s  (c) forward + CrossEntropyLoss + backward + torch.optim.AdamW on host-built pair batches
                         (d) CXRBertForRetrieval.fit_step
 Each variant: warm-up runs, then `--repeats` timed runs (host clock around a device synchronisation: the host work is part of what is
-compared); median, min and max are reported.  Writes profiles/retrieval_bench.json (and prints it).
+compared); median, min and max are reported.  mv_pair_assemble is timed on its own with device events against the bytes its feature
+gather reads and writes.  Writes profiles/retrieval_bench.json (and prints it).
 usage: python profiles/tools/retrieval_bench.py [--groups 4] [--batch 100] [--train-batch 16] [--repeats 5] [--warmup 2]"""
 import argparse
 import json
@@ -20,6 +21,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import medvill_amd as mv  # noqa: E402
+from medvill_amd import hip_ops as ops  # noqa: E402
 from medvill_amd.data import MaskDesc, RetrievalBank  # noqa: E402
 
 CLS, SEP = 101, 102
@@ -39,9 +41,22 @@ def timed(fn, warmup, repeats):
     return dict(median_s=statistics.median(ts), min_s=min(ts), max_s=max(ts), runs=len(ts))
 
 
+def event_ms(fn, iters=50):
+    for _ in range(5):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--groups", type=int, default=4)
+    ap.add_argument("--kernel-images", type=int, default=256, help="images of the bank mv_pair_assemble is timed over")
     ap.add_argument("--batch", type=int, default=100)
     ap.add_argument("--train-batch", type=int, default=16, help="positives per step (the batch holds twice as many pairs)")
     ap.add_argument("--repeats", type=int, default=5)
@@ -138,6 +153,27 @@ def main():
         res[name] = t
         print(name, json.dumps(t), file=sys.stderr, flush=True)
     res["train_speedup"] = res["train_forward_ce_backward_torch_adamw"]["median_s"] / res["train_fit_step"]["median_s"]
+
+    # mv_pair_assemble on its own at the banks' benchmark configuration (R = 64 pairs, 16-bit features), device events (launch after
+    # launch, the wrapper's allocations included).  The pairs rotate over a bank of --kernel-images images: with a bank larger than
+    # the 256 MiB Infinity Cache the gathered rows come from HBM, as they do in an epoch
+    R, n_k = 64, a.kernel_images
+    kb = RetrievalBank(model)
+    kb.add_texts(ids[:n_k], lens[:n_k]).add_images((torch.randn((n_k, N, 2048), generator=torch.Generator().manual_seed(2)),
+                                                    torch.arange(N).unsqueeze(0).repeat(n_k, 1)))
+    kp = [torch.from_numpy(np.stack([rng.integers(0, n_k, R), rng.integers(0, kb.n_texts, R)], 1).astype(np.int32)).to(dev)
+          for _ in range(16)]
+    turn = {"i": 0}
+
+    def assemble():
+        turn["i"] += 1
+        return ops.pair_assemble(kb.txt_ids, kb.txt_len, kb.img_feats, kb.img_pos, kp[turn["i"] % 16])
+
+    gather_bytes = 2 * R * N * 2048 * kb.img_feats.element_size()
+    k = {"mv_pair_assemble_ms": event_ms(assemble), "bank_feature_bytes": kb.img_feats.numel() * kb.img_feats.element_size(),
+         "assemble_gather_bytes": gather_bytes}                                # read + written by the feature gather
+    k["assemble_gather_GBps"] = gather_bytes / (k["mv_pair_assemble_ms"] * 1e-3) / 1e9
+    res["kernels"] = k
     with open(a.out, "w") as f:
         json.dump(res, f, indent=2)
     print(json.dumps(res))

@@ -172,9 +172,17 @@ SWEEP = [
     (3, 1, 64, 16, 2048, "f16", "random"),
     (64, 3, 1, 16, 8, "f32", "hash"),
 ]
-# the guard elements in front of every output of a sweep case; 3 puts the 16-bit feature rows off a 16-byte boundary, which takes the
-# copy's 2-byte path
+# the guard elements in front of every output of a sweep case; 3 puts the feature rows off a 16-byte boundary, which takes the copy's
+# element-by-element path ("odd-guard" cases)
 GUARD, GUARD_ODD = 16, 3
+# further cases of the assembly sweep, chosen for the feature copy (csrc/mv_bank.h): whole vectors off their alignment; N F = 20500 in
+# f32 -- two chunks, the last one unrolled round and a 5-vector remainder; 36936 in f16 -- a last chunk of 521 vectors, no whole round.
+# test_bank_cases_cpu.py shows which branches of the copy SWEEP + COPY_CASES reach.
+COPY_CASES = [
+    (17, 3, 3, 1, 8, "bf16", "odd-guard"),
+    (17, 3, 3, 5, 4100, "f32", "hash"),
+    (17, 3, 3, 9, 4104, "f16", "hash"),
+]
 
 
 def plan_case(kind, B=5, P=6, L=40, V=300, seed=0):

@@ -186,6 +186,14 @@ def sampler_cases():
 
 
 # ---------------------------------------------------------------------------------------------------- pair batches
+# (N, S, F) of the pair-assembly test, each in every encoding, from an aligned bank and from a view of it that starts PAIR_VIEW_OFFSET
+# elements in (off the 16-byte alignment).  N F = 20500 in f32: two chunks, the last one unrolled round and a 5-vector remainder; 36936
+# in f16: a last chunk of 521 vectors, no whole round.  test_bank_cases_cpu.py shows which branches of the shared copy the list reaches.
+PAIR_SHAPES = [(3, 5, 8), (16, 45, 2048), (5, 7, 9), (5, 7, 4100), (9, 7, 4104)]
+PAIR_DTYPES = ("f32", "f16", "bf16")
+PAIR_VIEW_OFFSET = 1
+
+
 def assemble(txt_ids, txt_len, img_feats, img_pos, pairs):
     """the assembled batch of mv_pair_assemble"""
     pairs = np.asarray(pairs)

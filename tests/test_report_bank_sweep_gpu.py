@@ -100,7 +100,7 @@ def _sweep_id(c):
     return "T{}-B{}-P{}-N{}-F{}-{}-{}".format(*c)
 
 
-@pytest.mark.parametrize("case", C.SWEEP + [(17, 3, 3, 1, 8, "bf16", "odd-guard")], ids=_sweep_id)
+@pytest.mark.parametrize("case", C.SWEEP + C.COPY_CASES, ids=_sweep_id)
 def test_assemble_and_plan_equal_the_restatement(case):
     T, B, max_pred, N, F, dtn, kind = case
     dt = DT[dtn]

@@ -87,9 +87,10 @@ def test_pair_negatives_on_hash_draws_read_back(n, classes):
 
 
 # ------------------------------------------------------------------------------------------------ mv_pair_assemble
-@pytest.mark.parametrize("shape", [(3, 5, 8), (N_REG, S_TXT, CFG.img_hidden), (5, 7, 9)])
-@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("shape", RC.PAIR_SHAPES)
+@pytest.mark.parametrize("dtype", [{"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[n] for n in RC.PAIR_DTYPES])
 def test_pair_assemble_is_bit_exact(shape, dtype):
+    assert RC.PAIR_SHAPES[1] == (N_REG, S_TXT, CFG.img_hidden)                    # the shape of the model tests below
     N, S, Fd = shape
     ids, lens, feats, pos = RC.make_banks(9, 7, N, S, Fd, seed=N + S)
     ft = torch.from_numpy(feats).to(dtype)
@@ -106,7 +107,8 @@ def test_pair_assemble_is_bit_exact(shape, dtype):
         assert cls_tok.tolist() == [[101]] * 7 and sep_tok.tolist() == [[102]] * 7
     out = ops.pair_assemble(bank.txt_ids, bank.txt_len, bank.img_feats, None, torch.tensor(pairs, dtype=torch.int32, device=DEV))
     assert out["pos"] is None and np.array_equal(out["n_ids"].cpu().numpy(), want["n_ids"])
-    unaligned = bank.img_feats.reshape(-1)[1:1 + 6 * N * Fd].view(6, N, Fd)       # a bank that is not 16-byte aligned: the narrow copy
+    o = RC.PAIR_VIEW_OFFSET
+    unaligned = bank.img_feats.reshape(-1)[o:o + 6 * N * Fd].view(6, N, Fd)       # a bank that is not 16-byte aligned: the narrow copy
     out = ops.pair_assemble(bank.txt_ids, bank.txt_len, unaligned, None, torch.tensor([[5, 0], [0, 1]], dtype=torch.int32, device=DEV))
     assert torch.equal(out["feats"], unaligned[[5, 0]])
 

@@ -1,5 +1,5 @@
 """The VQA bank without a GPU: the numpy restatements of tests/vqa_bank_cases.py against data.VqaBank.dense_targets and a direct scatter_
-per question, the branches of mv_vqa_assemble's launcher the case set reaches (its constants are read out of csrc/mv_vqa_bank.hip), the
+per question, the branches of mv_vqa_assemble's launcher the case set reaches (its constants are read out of csrc/mv_bank.h), the
 planted defects the sweep's comparison must catch, data.VqaBank's host side and the CPU-reachable half of the two entries' C ABI (each
 validates its arguments before it touches the HIP runtime)."""
 import ctypes

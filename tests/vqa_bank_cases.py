@@ -1,6 +1,6 @@
 """Shared definitions of the VQA-bank tests (no GPU, no package import): plain-numpy statements of what csrc/mv_vqa_bank.hip computes --
-mv_vqa_assemble's batch and mv_vqa_score's scores and counters --, of the launcher's chunk plan (its constants are read out of the
-source file, not repeated here), of the reference's target construction and type mapping, and the case generator of the sweeps.  Each
+mv_vqa_assemble's batch and mv_vqa_score's scores and counters --, of the reference's target construction and type mapping, and the
+case generator of the sweeps; the launcher's chunk plan is the shared one of tests/bank_cases.py.  Each
 restatement takes `defect=`: a planted mistake the comparison of the sweep must tell from the rule (test_vqa_bank_cases_cpu.py).
 
 The rule (include/medvill.h).  The reference's VQA-RAD loader (Downstream_task/report_generation_and_vqa/sc/data_loader.py:236-273)
@@ -9,9 +9,11 @@ a label listed twice keeps its LATER score.  Preprocess4Seq2seq lays a question 
 tokens and the [SEP] (:342-348, :392) and masks nothing (:378-381); the answer type strings map to 0 / 1 (:434-437).  The score of a
 prediction is the target's value at the predicted column (pytorch_pretrained_bert/model.py:1007-1012, 1023)."""
 import os
-import re
 
 import numpy as np
+
+import bank_cases
+from bank_cases import ALL_BRANCHES, ITEMSIZE, launch_plan          # noqa: F401  (the plan is the three bank kernels' one)
 
 PAD, SEP = 0, 102
 FAMILY_S2S, FAMILY_BAR, FAMILY_1D = 1, 2, 4
@@ -124,48 +126,9 @@ def metrics(counters):
 
 
 # ------------------------------------------------------------------------------------------------ the launcher's plan
-def source_constants(path=HIP_SOURCE):
-    """The `constexpr int NAME = value;` lines of the kernel file."""
-    return {m.group(1): int(m.group(2)) for m in re.finditer(r"constexpr\s+int\s+(\w+)\s*=\s*(\d+)\s*;", open(path).read())}
-
-
-def launch_plan(N, F, itemsize, aligned, k=None):
-    """mv_vqa_assemble's launcher, restated over the file's constants: -> dict(chunk, chunks, vec, branches) with `branches` the set of
-    paths the launch takes: 'elements' / 'vec' (the copy loop), 'vec_body' / 'vec_tail' / 'ragged_tail' (the unrolled rounds, the
-    remainder loop, a remainder that is no multiple of the block), 'one_chunk' / 'many_chunks', 'full_last_chunk' /
-    'partial_last_chunk', 'large_chunks' (the grid's second dimension capped), 'misaligned' (whole vectors, bases off 16 bytes)."""
-    k = k or source_constants()
-    per_vec = k["VEC_BYTES"] // itemsize
-    row = N * F
-    chunk = k["CHUNK_BYTES"] // itemsize
-    chunks = -(-row // chunk)
-    br = set()
-    if chunks > k["MAX_CHUNKS"]:
-        chunk = -(-(-(-row // k["MAX_CHUNKS"])) // per_vec) * per_vec
-        chunks = -(-row // chunk)
-        br.add("large_chunks")
-    vec = row % per_vec == 0 and aligned
-    if row % per_vec == 0 and not aligned:
-        br.add("misaligned")
-    br.add("vec" if vec else "elements")
-    br.add("one_chunk" if chunks == 1 else "many_chunks")
-    br.add("full_last_chunk" if row % chunk == 0 else "partial_last_chunk")
-    if vec:
-        round_ = k["UNROLL"] * k["NT"]
-        for c in range(chunks):
-            n4 = min(row - c * chunk, chunk) // per_vec
-            body = n4 // round_ * round_
-            if body:
-                br.add("vec_body")
-            if n4 > body:
-                br.add("vec_tail")
-                if (n4 - body) % k["NT"]:
-                    br.add("ragged_tail")
-    return dict(chunk=chunk, chunks=chunks, vec=vec, branches=br)
-
-
-ALL_BRANCHES = {"elements", "vec", "vec_body", "vec_tail", "ragged_tail", "one_chunk", "many_chunks", "full_last_chunk",
-                "partial_last_chunk", "large_chunks", "misaligned"}
+def source_constants():
+    """The constants of the shared gather (csrc/mv_bank.h) and of the kernel file."""
+    return bank_cases.source_constants(bank_cases.BANK_HEADER, HIP_SOURCE)
 
 
 # ------------------------------------------------------------------------------------------------ cases
@@ -271,7 +234,6 @@ SWEEP = [
     (6, 458, 46, 2, 8, "f32", None, None, GUARD_ODD),
     (1, 17, 2, 1, 16777244, "f32", None, 8, GUARD),               # more chunks than the grid's cap: larger chunks
 ]
-ITEMSIZE = {"f32": 4, "bf16": 2, "f16": 2}
 
 
 def sweep_bank(case):
