@@ -760,6 +760,36 @@ int mv_vqa_score(const int64_t* pred, const int32_t* idx, int B, int n_questions
                  const float* ans_score, int nnz, const int32_t* ans_type, const int32_t* group, int G, float* score,
                  unsigned long long* counters, void* stream);
 
+/* ---- diagnosis classification from a device-resident bank (csrc/mv_clf_bank.hip) -------------------------------------------
+ * The reference's JsonlDataset + collate_fn (Downstream_task/Classification/mmbt/data/dataset.py:36-85, data/helpers.py:73-98) and
+ * the counts behind model_eval's metrics (mmbt/main.py:138-193).  Additive entry points.
+ *
+ * The bank: txt_ids int64 [n_samples, T] (each row tokens + [SEP] + [PAD]...), txt_len int32 [n_samples] (counting the [SEP]), s_img
+ *     int32 [n_samples] (the image of a sample; clamped into the image bank), lab_bits int32 [n_samples, W], W = ceil(C / 32): class c
+ *     is bit c % 32 of word c / 32, img_feats [n_images, N, F] (dtype), img_pos int64 [n_images, N].
+ * mv_clf_assemble: one launch per batch, grid (B, chunks of the N F feature row).  idx int32 [B] (an index outside the bank is clamped
+ *     into it), family int32 [B] (nullable = 4, the 1-D family).  For slot i with sample d = idx[i], image m = s_img[d] and
+ *     len = txt_len[d] clamped to [1, T] it writes input_txt int64 [B, T] (the bank row as it is), segment int64 [B, T] (1 for t < len,
+ *     else 0), desc int32 [B, 3] = {family, N+2, N+2+len}, feats [B, N, F] (dtype) = img_feats[m] bit for bit, pos_out int64 [B, N] =
+ *     img_pos[m], target f32 [B, C] = 1.0 where the class's bit is set, else 0.0.  No atomics: fully defined and bitwise reproducible.
+ *     T <= 1024, C <= 1024, N F < 2^31, B T < 2^31.
+ * mv_clf_counts: probs f32 [n, ld] (ld >= C; the sigmoid probabilities mv_bce_multilabel writes), idx int32 [n] (the sample of each
+ *     row; clamped into the n_items samples of lab_bits).  counters uint64 [C + 1, 7], ACCUMULATED (zero them first): rows 0 .. C-1
+ *     one class each over the n samples, row C every one of the n C (sample, class) elements as ONE list (the micro average).  Columns
+ *     {n_pos, n_neg, gt, eq, tp, fp, fn}: the elements whose label bit is set / clear; the pairs (p positive, q negative) of the list
+ *     with prob_p > prob_q / prob_p == prob_q (f32 comparison; -0 equals +0; a NaN is unspecified); the elements with prob > 0.5f
+ *     and the bit set (tp) or clear (fp), and those at or below with the bit set (fn).  AUROC = (2 gt + eq) / (2 n_pos n_neg), the
+ *     tie-averaged rank statistic.  Integer counts, added with 64-bit integer atomics: the result does not depend on the order in
+ *     which blocks finish.  Pair counting is quadratic: n C <= 2^21, C <= 1024.
+ * Null pointers (family excepted), non-positive sizes, ld < C: MV_E_ARG; unknown dtype: MV_E_DTYPE; T > 1024, C > 1024, N F or B T
+ * past 32-bit indexing, n C > 2^21: MV_E_SHAPE.  All of it is checked before anything touches the HIP runtime.  */
+int mv_clf_assemble(const int64_t* txt_ids, const int32_t* txt_len, const int32_t* s_img, const int32_t* lab_bits, int n_samples,
+                    const void* img_feats, int dtype, const int64_t* img_pos, int n_images, const int32_t* idx, const int32_t* family,
+                    int B, int N, int T, int F, int C, int64_t* input_txt, int64_t* segment, int32_t* desc, void* feats,
+                    int64_t* pos_out, float* target, void* stream);
+int mv_clf_counts(const float* probs, int ld, const int32_t* idx, int n, const int32_t* lab_bits, int n_items, int C,
+                  unsigned long long* counters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,9 @@ PROTOTYPES = {
     # VQA from a device-resident question bank (csrc/mv_vqa_bank.hip)
     "mv_vqa_assemble": [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "mv_vqa_score": [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp],
+    # classification from a device-resident bank (csrc/mv_clf_bank.hip)
+    "mv_clf_assemble": [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+    "mv_clf_counts": [vp, i32, vp, i32, vp, i32, i32, vp, vp],
 }
 # include/medvill_debug.h: exported by libmedvill_hip_dbg.so only
 DEBUG_PROTOTYPES = {"mv_debug_set_knob": [i32, i32], "mv_debug_get_knob": [i32]}

@@ -7,6 +7,7 @@
     loss = criterion(out, tgt); loss.backward(); optimizer.step()                     # main.py:213-217, verbatim
     loss = model(..., labels=tgt)                                                     # or: the fused loss + model.clf_stats
     probs = model.predict(...)                                                        # sigmoid probabilities under no_grad
+    loss = model.fit_step(bank, idx, optimizer); out = model.evaluate(bank)           # from a data.ClassificationBank (DESIGN.md "8t")
 
 The encoder runs its last layer's per-row work on the B [CLS] rows only (Engine.encoder_forward, tail_rows=[]), as VQA training; the
 engine's pooler feeds `clf`; unlike VQA the pooler gets a gradient (Engine._pooler_backward), the ITM and MLM heads get none.  `clf`
@@ -68,7 +69,10 @@ class CXRBertForClassification(FlatHead):
          labels None -> differentiable f32 logits [B, C];  labels [B, C] multi-hot float -> the mean BCEWithLogitsLoss (with
          `pos_weight` when set), and `model.clf_stats` f32 [3, C] on the device += {tp, fp, fn} at threshold 0.5 (reset_stats() clears).
     .bert is the CXRBERT (its pooler is the head's first half), .clf the Linear(H, C) whose Parameters are views of the head's flat
-    buffer (task.FlatHead)."""
+    buffer (task.FlatHead).
+    fit_step / evaluate: the same step, and the reference's model_eval with its per-class / macro / micro AUROC and F1, from a
+    device-resident data.ClassificationBank -- the batch built by one HIP launch, the metrics from one launch of integer counts and one
+    read-back per evaluation (DESIGN.md "8t")."""
 
     _head_keys = CLF_KEYS
     _padded_key = CLF_KEYS[0]
@@ -201,6 +205,85 @@ class CXRBertForClassification(FlatHead):
             ops.bce_multilabel(logits, self.n_classes, ld=self.Ap, probs=probs)
         return probs
 
+    # ------------------------------------------------------------------ steps from a device-resident bank
+    def _check_bank(self, bank):
+        if bank.n_samples == 0 or bank.n_images == 0:
+            raise ValueError("the bank is empty (ClassificationBank.add_samples, add_images)")
+        if bank.n_classes != self.n_classes:
+            raise ValueError(f"the bank holds targets over {bank.n_classes} classes, the classifier has {self.n_classes}")
+        Lq = int(bank.img_feats.shape[1]) + int(bank.txt_ids.shape[1]) + 2
+        if Lq > self.bert.cfg.max_pos:
+            raise ValueError(f"the bank's sequences hold {Lq} positions ([CLS] + regions + [SEP] + text), max_position_embeddings is "
+                             f"{self.bert.cfg.max_pos}")
+
+    def fit_step(self, bank, idx, optimizer, mode="bi"):
+        """One fine-tuning step (mmbt/main.py:208-217) from a data.ClassificationBank: optimizer.zero_grad(), the batch of the samples
+        `idx` (one mv_clf_assemble launch), the loss node of forward(..., labels=target), its backward and optimizer.step().  mode:
+        "s2s" / "bi" / "bar" or one per sample; "bi" is the reference's 1-D mask.  Returns the loss as a device scalar; clf_stats is
+        updated as after forward.  Refused: several ranks, an empty bank, a bank over another class count, sequences longer than
+        max_position_embeddings, a host idx outside the bank (IndexError)."""
+        check_single_rank("CXRBertForClassification", "data-parallel fine-tuning is not supported (the head's gradients would not be "
+                          "all-reduced); fine-tune on one rank, or run evaluate")
+        self._check_bank(bank)
+        with self._engine_state("training", "keep_acts"):
+            optimizer.zero_grad()
+            with torch.enable_grad():
+                cls_tok, input_txt, desc, segment, img, sep_tok, target = bank.assemble(idx, mode=mode)
+                loss = self(cls_tok, input_txt, desc, segment, img, sep_tok, labels=target)
+                loss.backward()
+        optimizer.step()
+        return loss.detach()
+
+    @torch.no_grad()
+    def evaluate(self, bank, idx=None, batch_size=64, mode="bi"):
+        """The reference's model_eval (mmbt/main.py:138-193) over the samples `idx` of a data.ClassificationBank (None: every sample, in
+        order), in eval mode and without gradients; a last partial batch is allowed.  Every batch's sigmoid probabilities go into one
+        [n, C] device buffer and its BCE sum into its slot of a per-batch buffer; one mv_clf_counts launch turns the probabilities and the
+        bank's label bits into integer counts, and ONE read-back brings the counts and the loss bits over.  -> dict(loss (the mean of
+        the batch means, main.py:145,158), auroc_per_class, macro_auroc, micro_auroc, macro_f1, micro_f1 (metrics_from_counters), n,
+        counters int64 [C + 1, 7] on the host, probs f32 [n, C] on the device).  The engine's training / keep-activations /
+        dropout-counter state is restored.  Pair counting is quadratic: n C <= 2^21 (beyond: metrics() on the host)."""
+        if int(batch_size) < 1:
+            raise ValueError("batch_size >= 1")
+        self._check_bank(bank)
+        eng = self.bert.engine
+        # `take`: what the batches are cut from -- a host list stays a host list (its descriptors need no read-back)
+        if torch.is_tensor(idx) and idx.device.type != "cpu":
+            if idx.dtype != torch.int32 or idx.dim() != 1 or idx.numel() == 0:
+                raise TypeError("idx on the device: non-empty int32 [n]")
+            dev_idx = take = idx.contiguous()
+        else:
+            take = bank.host_idx(torch.arange(bank.n_samples) if idx is None else idx)
+            dev_idx = take.to(torch.int32).to(eng.device)
+        n, C, bs = int(dev_idx.numel()), self.n_classes, int(batch_size)
+        if n * C > ops.CLF_MAX_ELEMS:
+            raise ValueError(f"evaluate: {n} samples x {C} classes is past the {ops.CLF_MAX_ELEMS} elements mv_clf_counts pairs up; "
+                             "collect predict()'s probabilities and use classification.metrics() on the host")
+        if not isinstance(mode, str) and len(mode) != n:
+            raise ValueError(f"mode: one name, or one per sample ({n})")
+        n_batches = (n + bs - 1) // bs
+        probs = torch.empty((n, C), dtype=torch.float32, device=eng.device)
+        sums = torch.zeros(n_batches, dtype=torch.float32, device=eng.device)
+        with self._engine_state("training", "keep_acts", "drop_counter"):
+            self._prepare(False)
+            eng.training = False
+            for k, s in enumerate(range(0, n, bs)):
+                e = min(n, s + bs)
+                cls_tok, input_txt, desc, segment, (feats, pos), sep_tok, target = bank.assemble(
+                    take[s:e], mode=mode if isinstance(mode, str) else list(mode[s:e]))
+                logits = self._encode_and_classify(cls_tok, input_txt, desc, segment, feats, pos, sep_tok)
+                ops.bce_multilabel(logits, C, R=e - s, ld=self.Ap, target=target, pos_weight=self.pos_weight, loss=sums[k:k + 1],
+                                   probs=probs[s:e])
+            counters = ops.clf_counts(probs, dev_idx, bank.lab_bits, C)
+        # the one read-back: the integer counters and the bits of the batches' f32 BCE sums
+        host = torch.cat([counters.reshape(-1), sums.view(torch.int32).to(torch.int64)]).cpu()
+        cnt = host[:counters.numel()].view(C + 1, ops.CLF_NCOUNT)
+        bce = host[counters.numel():].to(torch.int32).view(torch.float32)
+        sizes = torch.tensor([min(n, s + bs) - s for s in range(0, n, bs)], dtype=torch.float32) * float(C)
+        out = metrics_from_counters(cnt)
+        out.update(loss=float((bce / sizes).double().mean()), n=n, counters=cnt, probs=probs)
+        return out
+
     # ------------------------------------------------------------------ state dict (MultimodalBertClf's layout)
     def state_dict(self, *a, **k):
         """CXRBERT's enc.* names (aliases included) plus clf.weight / clf.bias -- no mlm.* / itm.* (the model has neither head)."""
@@ -257,9 +340,35 @@ def metrics(probs, targets, counters=None):
         cnt = torch.stack([(pred & pos).sum(0), (pred & ~pos).sum(0), (~pred & pos).sum(0)]).double()
     else:
         cnt = torch.as_tensor(counters).detach().double().cpu().reshape(3, C)
-    tp, fp, fn = cnt[0], cnt[1], cnt[2]
+    macro_f1, micro_f1 = _f1(cnt[0], cnt[1], cnt[2])
+    return dict(auroc_per_class=per, macro_auroc=sum(per) / C, micro_auroc=_auroc(p.reshape(-1), t.reshape(-1)),
+                macro_f1=macro_f1, micro_f1=micro_f1)
+
+
+def _f1(tp, fp, fn):
+    """(macro, micro) F1 from f64 [C] counts; a zero denominator scores 0."""
     den = 2 * tp + fp + fn
     f1 = torch.where(den > 0, 2 * tp / den.clamp(min=1), torch.zeros_like(den))
     mden = float(2 * tp.sum() + fp.sum() + fn.sum())
-    return dict(auroc_per_class=per, macro_auroc=sum(per) / C, micro_auroc=_auroc(p.reshape(-1), t.reshape(-1)),
-                macro_f1=float(f1.mean()), micro_f1=(float(2 * tp.sum()) / mden if mden > 0 else 0.0))
+    return float(f1.mean()), (float(2 * tp.sum()) / mden if mden > 0 else 0.0)
+
+
+def metrics_from_counters(counters):
+    """mv_clf_counts' integer counters [C + 1, 7] = {n_pos, n_neg, gt, eq, tp, fp, fn} (rows 0 .. C-1 one class each, row C all n C
+    elements as one list) -> what `metrics` returns, formed from exact integers: AUROC = (2 gt + eq) / (2 n_pos n_neg) -- the
+    tie-averaged rank statistic of _auroc, bit for bit -- or 0 when a label value is missing (main.py:167-171); macro AUROC the mean
+    with those zeros; F1 from the class rows at the reference's threshold, zero on a zero denominator."""
+    c = torch.as_tensor(counters).detach().cpu().to(torch.int64)
+    if c.dim() != 2 or c.shape[1] != 7 or c.shape[0] < 2:
+        raise ValueError("metrics_from_counters: counters [C + 1, 7]")
+    C = int(c.shape[0]) - 1
+    rows = c.tolist()
+
+    def auroc(r):
+        n_pos, n_neg, gt, eq = r[:4]
+        return (2 * gt + eq) / (2 * n_pos * n_neg) if n_pos and n_neg else 0.0
+
+    per = [auroc(r) for r in rows[:C]]
+    cls = c[:C].double()
+    macro_f1, micro_f1 = _f1(cls[:, 4], cls[:, 5], cls[:, 6])
+    return dict(auroc_per_class=per, macro_auroc=sum(per) / C, micro_auroc=auroc(rows[C]), macro_f1=macro_f1, micro_f1=micro_f1)

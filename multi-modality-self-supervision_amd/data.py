@@ -631,3 +631,153 @@ class VqaBank(DeviceBank):
         out = ops.vqa_assemble(self.txt_ids, self.txt_len, self.q_img, self.ans_ptr, self.ans_label, self.ans_score, self.ans_type,
                                self.img_feats, self.img_pos, dev_idx, self.n_answers, family=fam_host.to(self.device))
         return self._batch(out, host) + (out["target"], out["ans_type"])
+
+
+# ---------------------------------------------------------------------------------------------------- classification bank
+CLF_MAX_CLASSES = 1024             # mv_clf_assemble / mv_clf_counts
+
+
+class ClassificationBank(DeviceBank):
+    """A diagnosis-classification data set resident on the device: sample i = (image s_img[i], text i, its multi-hot target), what the
+    reference's JsonlDataset + collate_fn build per sample on the host and push across every step (Downstream_task/Classification/mmbt/
+    data/dataset.py:36-85, data/helpers.py:73-98).  An image passes the region encoder once, a batch comes out of one mv_clf_assemble
+    launch, and a whole evaluation's metrics follow from one mv_clf_counts launch over the stored label bits.
+      add_images(input_img)   as DeviceBank.add_images, once per distinct image
+      add_samples(ids, lengths, labels, image_item=None)
+                              ids int64 [n, T] / lengths [n]: add_texts' layout (tokens + [SEP] + [PAD]..., lengths count the [SEP]) --
+                              what dataset.py:39-44,80-81 leaves after it drops the leading [SEP]; labels: a multi-hot [n, C] array (any
+                              value > 0.5 is set) or one ragged list of class indices per sample (None or empty: an all-zero target; a
+                              repeated index is allowed); image_item int [n]: the item of the image bank, None = item i is image i counted
+                              from the samples already in the bank.  Mapping label strings to indices (the reference's '' -> 'Others'
+                              included, :58-64) and drop_img_percent (one grey image, image_item pointing at it) stay with the caller.
+                              Refused (ValueError, nothing is added): an index outside [0, C), a multi-hot array of another width, a
+                              negative or non-integer image_item, wrong counts.
+      assemble(idx, mode)     -> (cls_tok, input_txt, attn_mask, segment, input_img, sep_tok, target): the arguments of
+                              CXRBertForClassification.forward with attn_mask a MaskDesc and target f32 [B, C].  mode "s2s" / "bi" / "bar"
+                              or one per sample (ReportBank.assemble's rule); the default "bi" is the 1-D family, the reference's
+                              mask_tensor.  idx given on the host is checked there (IndexError outside the bank, ValueError when a listed
+                              sample names an image the image bank does not hold) and the descriptors' host copy comes from the host
+                              lengths (no read-back); idx on the device (int32) is clamped into the bank by the kernel.
+      dense_targets(idx)      f32 [len(idx), C] built on the host: the restated reference (:57-64).
+      pos_weight()            f32 [C] as get_criterion forms it (mmbt/main.py:96-98) over the bank's samples.
+    Storage on the device: s_img int32 [n], lab_bits int32 [n, W], W = ceil(C / 32), class c = bit c % 32 of word c / 32; host copies of
+    the lengths, s_img and the bits."""
+
+    def __init__(self, model=None, device=None, feat_dtype=None, n_classes=14):
+        super().__init__(model, device, feat_dtype)
+        self.n_classes = int(n_classes)
+        if not 1 <= self.n_classes <= CLF_MAX_CLASSES:
+            raise ValueError(f"ClassificationBank: 1 <= n_classes <= {CLF_MAX_CLASSES}")
+        self.n_words = (self.n_classes + 31) // 32
+        self.s_img = self.lab_bits = None
+        self._s_img_host = torch.zeros(0, dtype=torch.int64)
+        self._bits_host = torch.zeros((0, self.n_words), dtype=torch.int32)
+
+    @property
+    def n_samples(self):
+        return 0 if self.s_img is None else int(self.s_img.numel())
+
+    def _multi_hot(self, labels, n):
+        """labels -> bool [n, C] on the host."""
+        C = self.n_classes
+        dense = None
+        if torch.is_tensor(labels) and labels.dim() == 2:
+            dense = labels.detach().cpu()
+        elif hasattr(labels, "ndim") and getattr(labels, "ndim") == 2 and getattr(labels, "dtype", None) != object:
+            dense = torch.as_tensor(labels)
+        if dense is not None:
+            if tuple(dense.shape) != (n, C):
+                raise ValueError(f"add_samples: a multi-hot label array is [n, C] = [{n}, {C}], got {tuple(dense.shape)}")
+            return dense.to(torch.float64) > 0.5
+        if len(labels) != n:
+            raise ValueError("add_samples: one label list per sample")
+        hot = torch.zeros((n, C), dtype=torch.bool)
+        for i in range(n):
+            li = [] if labels[i] is None else torch.as_tensor(labels[i]).reshape(-1).tolist()
+            if any(int(l) != l or not 0 <= int(l) < C for l in li):
+                raise ValueError(f"add_samples: sample {i} lists a class outside [0, {C})")
+            if li:
+                hot[i, [int(l) for l in li]] = True
+        return hot
+
+    def _pack(self, hot):
+        """bool [n, C] -> int32 [n, W]: class c is bit c % 32 of word c / 32."""
+        n, C, W = int(hot.shape[0]), self.n_classes, self.n_words
+        padded = torch.zeros((n, W * 32), dtype=torch.int64)
+        padded[:, :C] = hot.to(torch.int64)
+        words = (padded.view(n, W, 32) << torch.arange(32, dtype=torch.int64)).sum(dim=2)          # in [0, 2^32)
+        return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+    def _unpack(self, bits):
+        """int32 [m, W] -> bool [m, C]."""
+        w = bits.to(torch.int64) & 0xFFFFFFFF
+        return ((w.unsqueeze(2) >> torch.arange(32, dtype=torch.int64)) & 1).reshape(bits.shape[0], -1)[:, :self.n_classes].bool()
+
+    def add_samples(self, ids, lengths, labels, image_item=None):
+        ids = torch.as_tensor(ids)
+        n = int(ids.shape[0]) if ids.dim() == 2 else -1
+        if n < 1 or labels is None:
+            raise ValueError("add_samples: ids [n, T], one length and one label row or list (and image item) per sample")
+        if image_item is None:
+            img = torch.arange(self.n_samples, self.n_samples + n, dtype=torch.int64)
+        else:
+            img = torch.as_tensor(image_item).reshape(-1)
+            if img.numel() != n:
+                raise ValueError("add_samples: one image item per sample")
+            if img.dtype.is_floating_point or img.dtype == torch.bool or int(img.min()) < 0 or int(img.max()) > 2 ** 31 - 1:
+                raise ValueError("add_samples: image_item holds non-negative integers")
+            img = img.to(torch.int64).cpu()
+        bits = self._pack(self._multi_hot(labels, n))
+        self.add_texts(ids, lengths)                         # (its own refusals come before anything of the samples is stored)
+        self._s_img_host = torch.cat([self._s_img_host, img])
+        self._bits_host = torch.cat([self._bits_host, bits])
+        cat = lambda old, new: new if old is None else torch.cat([old, new])
+        self.s_img = cat(self.s_img, img.to(torch.int32).to(self.device).contiguous())
+        self.lab_bits = cat(self.lab_bits, bits.to(self.device).contiguous())
+        return self
+
+    def dense_targets(self, idx):
+        idx = torch.as_tensor(idx).reshape(-1).to(torch.int64).cpu()
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.n_samples):
+            raise IndexError(f"idx outside the bank of {self.n_samples} samples")
+        return self._unpack(self._bits_host.index_select(0, idx)).to(torch.float32)
+
+    def pos_weight(self):
+        n = self.n_samples
+        if n == 0:
+            raise ValueError("ClassificationBank.pos_weight: the bank is empty (add_samples)")
+        freqs = self._unpack(self._bits_host).sum(dim=0).tolist()
+        if min(freqs) == 0:
+            raise ValueError(f"ClassificationBank.pos_weight: class {freqs.index(0)} has no positive sample (the reference would hand "
+                             "BCEWithLogitsLoss an infinite weight)")
+        negative = [n - f for f in freqs]
+        return (torch.FloatTensor(freqs) / torch.FloatTensor(negative)) ** -1          # main.py:96-98, verbatim
+
+    def _check_filled(self):
+        n = self.n_samples
+        if n == 0 or self.n_images == 0:
+            raise ValueError("ClassificationBank: the bank is empty (add_samples, add_images)")
+        if n != self.n_texts:
+            raise ValueError(f"ClassificationBank: {self.n_texts} text rows for {n} samples: fill the bank with add_samples, not add_texts")
+
+    def host_idx(self, idx):
+        """A host index list, checked against both banks: -> int64 [B]."""
+        self._check_filled()
+        return self._check_images(self._index_list(idx, self.n_samples, "samples"))
+
+    def _check_images(self, host_idx):
+        if int(self._s_img_host.index_select(0, host_idx).max()) >= self.n_images:
+            raise ValueError(f"a listed sample names an image outside the image bank of {self.n_images}")
+        return host_idx
+
+    def assemble(self, idx, mode="bi"):
+        from . import hip_ops as ops
+        self._check_filled()
+        dev_idx, host_idx = self._indices(idx, self.n_samples, "samples")
+        if host_idx is not None:
+            self._check_images(host_idx)
+        fam_host = self._families(mode, int(dev_idx.numel()))
+        host = None if host_idx is None else self.host_descriptors(host_idx, fam_host)
+        out = ops.clf_assemble(self.txt_ids, self.txt_len, self.s_img, self.lab_bits, self.img_feats, self.img_pos, dev_idx,
+                               self.n_classes, family=fam_host.to(self.device))
+        return self._batch(out, host) + (out["target"],)

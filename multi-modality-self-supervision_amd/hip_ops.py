@@ -906,7 +906,7 @@ def pair_negatives(idx, n, key=0, step=0, class_id=None, draws=None):
 
 
 def _bank_check(who, txt_ids, txt_len, img_feats, img_pos, idx, family=None, per_text=(), pairs=False):
-    """What the three *_assemble wrappers check alike: -> (text rows, T, images, N, F, samples).  idx: the int32 index list [B], or
+    """What the four *_assemble wrappers check alike: -> (text rows, T, images, N, F, samples).  idx: the int32 index list [B], or
     (pairs) the [R, 2] (image item, text item) list; per_text: further int32 tensors with one entry per text row; img_pos: None where
     the caller allows a bank without positions.  (These run once per batch next to a 25 us kernel: plain loops, no generators.)"""
     i32 = (txt_len, idx, *per_text) if family is None else (txt_len, idx, family, *per_text)
@@ -1090,3 +1090,55 @@ def vqa_score(pred, idx, ans_ptr, ans_label, ans_score, ans_type, group=None, G=
                              L.ptr(ans_type), L.ptr(group), G, L.ptr(score), L.ptr(counters), L.stream_ptr())
     L.check(rc, f"mv_vqa_score(B={B},G={G})")
     return score, counters
+
+
+# ---------------------------------------------------------------------------------------------------- classification bank (csrc/mv_clf_bank.hip)
+CLF_MAX_CLASSES = 1024          # mv_clf_assemble / mv_clf_counts: C <= 1024 (include/medvill.h)
+CLF_MAX_ELEMS = 1 << 21         # mv_clf_counts: n C <= 2^21 (pair counting is quadratic)
+CLF_NCOUNT = 7                  # n_pos, n_neg, gt, eq, tp, fp, fn
+
+
+def _clf_bits_check(who, lab_bits, C):
+    L.require_cuda(lab_bits)
+    if lab_bits.dtype != torch.int32 or lab_bits.dim() != 2 or lab_bits.shape[1] != (C + 31) // 32 or not lab_bits.is_contiguous():
+        raise TypeError(f"{who}: lab_bits contiguous int32 [samples, ceil(C / 32)]")
+    return int(lab_bits.shape[0])
+
+
+def clf_assemble(txt_ids, txt_len, s_img, lab_bits, img_feats, img_pos, idx, n_classes, family=None):
+    """Classification batches from the sample bank (see mv_clf_assemble): -> dict(input_txt, segment, desc, feats, pos, target)."""
+    C = int(n_classes)
+    n, T, n_img, N, F, B = _bank_check("clf_assemble", txt_ids, txt_len, img_feats, img_pos, idx, family, per_text=(s_img,))
+    if _clf_bits_check("clf_assemble", lab_bits, C) != n:
+        raise ValueError("clf_assemble: one row of label bits per text row")
+    out = _bank_outputs(B, T, N, F, img_feats)
+    out["target"] = torch.empty((B, C), dtype=torch.float32, device=idx.device)
+    rc = _lib().mv_clf_assemble(L.ptr(txt_ids), L.ptr(txt_len), L.ptr(s_img), L.ptr(lab_bits), n, L.ptr(img_feats), L.dt_of(img_feats),
+                                L.ptr(img_pos), n_img, L.ptr(idx), L.ptr(family), B, N, T, F, C, L.ptr(out["input_txt"]),
+                                L.ptr(out["segment"]), L.ptr(out["desc"]), L.ptr(out["feats"]), L.ptr(out["pos"]), L.ptr(out["target"]),
+                                L.stream_ptr())
+    if rc:
+        L.check(rc, f"mv_clf_assemble(B={B},N={N},T={T},F={F},C={C})")
+    return out
+
+
+def clf_counts(probs, idx, lab_bits, n_classes, counters=None):
+    """The integer counts of an evaluation (see mv_clf_counts): probs f32 [n, ld >= C] (rows may be strided), idx int32 [n] ->
+    counters int64 [C + 1, 7] = {n_pos, n_neg, gt, eq, tp, fp, fn} per class and, in row C, over all n C elements as one list;
+    `counters` (on the device) is accumulated into when given."""
+    C = int(n_classes)
+    L.require_cuda(probs, idx, counters)
+    if probs.dtype != torch.float32 or idx.dtype != torch.int32:
+        raise TypeError("clf_counts: probs f32, idx int32")
+    if probs.dim() != 2 or probs.shape[1] < C or probs.stride(1) != 1 or probs.stride(0) < probs.shape[1] or idx.dim() != 1 \
+            or idx.shape[0] != probs.shape[0] or not idx.is_contiguous():
+        raise ValueError("clf_counts: probs [n, >= C] with unit column stride and contiguous idx [n]")
+    n_items, n = _clf_bits_check("clf_counts", lab_bits, C), int(probs.shape[0])
+    if counters is None:
+        counters = torch.zeros((C + 1, CLF_NCOUNT), dtype=torch.int64, device=probs.device)
+    elif counters.dtype != torch.int64 or counters.numel() != (C + 1) * CLF_NCOUNT or not counters.is_contiguous():
+        raise TypeError(f"clf_counts: counters int64 [{C + 1}, {CLF_NCOUNT}]")
+    rc = _lib().mv_clf_counts(L.ptr(probs), int(probs.stride(0)), L.ptr(idx), n, L.ptr(lab_bits), n_items, C, L.ptr(counters),
+                              L.stream_ptr())
+    L.check(rc, f"mv_clf_counts(n={n},C={C})")
+    return counters
