@@ -790,6 +790,34 @@ int mv_clf_assemble(const int64_t* txt_ids, const int32_t* txt_len, const int32_
 int mv_clf_counts(const float* probs, int ld, const int32_t* idx, int n, const int32_t* lab_bits, int n_items, int C,
                   unsigned long long* counters, void* stream);
 
+/* ---- corpus BLEU-1..4 of generated reports (csrc/mv_bleu.hip) ---------------------------------------------------------------
+ * The reference's evaluation of report generation (Downstream_task/report_generation_and_vqa/sc/generation_decode.py:480-498,
+ * detokenize :97-104, sc/bleu.py:16-64): nltk's corpus_bleu over ' '.join(detokenize(tokens)).split(' ') against
+ * gt_caption.split(' ').  Additive entry points.
+ *
+ * Word keys: a word is named by the polynomial hash of its UTF-8 bytes modulo 2^64 with a fixed odd multiplier P (report_eval.py),
+ *     key(a + b) = key(a) P^len(b) + key(b), stored as the int64 of the same bits.  Equal keys are taken for equal words.  The
+ *     tables, one entry per vocabulary id: tok_key (the whole token string, with its ## where it has one), tail_key (tok[2:] of a
+ *     token that starts with ##), tail_pow (P^len(tok[2:]), 0 for a token that is no continuation); empty_key = key('').
+ * mv_bleu_words: ids int64 [n, T] with row stride ld >= T.  A row ends before its first eos_id or pad_id, or at T; an id outside
+ *     [0, V) ends it as pad_id does.  A kept token with tail_pow != 0 that is not the row's first extends the current word (key =
+ *     key tail_pow + tail_key); every other kept token starts a word with tok_key (a leading ##x keeps its ##).  A row without a kept
+ *     token holds the one word empty_key.  word_key int64 [n, T]: the row's words in order, 0 behind them; n_words int32 [n].  No
+ *     atomics on global memory: bitwise reproducible.  T <= 1024, V <= 2^20, n <= 2^20.
+ * mv_bleu_counts: hyp_key int64 [n, Th] / hyp_n int32 [n] (mv_bleu_words' outputs; a count is clamped to [0, Th]), ref_key int64
+ *     [n_items, Tr] / ref_n int32 [n_items], idx int32 [n]: row i is scored against item idx[i], clamped into the bank.  counters
+ *     uint64 [10] = {num_1..num_4, den_1..den_4, hyp_len, ref_len}, ACCUMULATED (zero them first): per sample with Lh hypothesis and
+ *     Lr reference words, num_o += the sum over the distinct hypothesis o-grams g of min(count_hyp(g), count_ref(g)) -- the o words
+ *     compared one by one --, den_o += max(1, Lh - o + 1) (nltk's modified_precision), hyp_len += Lh, ref_len += Lr.  Integer
+ *     counts added with 64-bit integer atomics: the result does not depend on the order in which blocks finish.  Th, Tr <= 1024,
+ *     n <= 2^20.
+ * Null pointers, non-positive sizes, ld < T: MV_E_ARG; T, Th or Tr > 1024, V > 2^20, n > 2^20: MV_E_SHAPE.  All of it is checked
+ * before anything touches the HIP runtime.  */
+int mv_bleu_words(const int64_t* ids, int ld, int n, int T, const int64_t* tok_key, const int64_t* tail_key, const int64_t* tail_pow,
+                  int V, int64_t eos_id, int64_t pad_id, int64_t empty_key, int64_t* word_key, int32_t* n_words, void* stream);
+int mv_bleu_counts(const int64_t* hyp_key, int Th, const int32_t* hyp_n, int n, const int64_t* ref_key, int Tr, const int32_t* ref_n,
+                   int n_items, const int32_t* idx, unsigned long long* counters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,6 @@ from .vqa import CXRBertForVQA  # noqa: F401
 from .classification import CXRBertForClassification  # noqa: F401
 from .report_finetune import CXRBertForReportFinetune  # noqa: F401
 from .image import ImageEncoder_cnn  # noqa: F401
-from . import beam, checkpoint, classification, data, dist, hip_ops, losses, optim, report_finetune, vqa  # noqa: F401
+from . import beam, checkpoint, classification, data, dist, hip_ops, losses, optim, report_eval, report_finetune, vqa  # noqa: F401
 
 __all__ = ["Engine", "ModelConfig", "param_layout", "CXRBERT", "CXRBERT_Trainer", "TrainStep", "CXRBertForRetrieval", "CXRBertForGeneration", "CXRBertForVQA", "CXRBertForClassification", "CXRBertForReportFinetune", "ImageEncoder_cnn", "data"]

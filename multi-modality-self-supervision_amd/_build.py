@@ -19,7 +19,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libmedvill_hip.so")
 LIB_DBG = os.path.join(HERE, "libmedvill_hip_dbg.so")
 SOURCES = ["mv_gemm_ring_tn.hip", "mv_gemm_ring_tn4.hip", "mv_gemm_ring_nt.hip", "mv_gemm_ring_nn.hip", "mv_gemm_ring_tnn.hip", "mv_gemm.hip", "mv_attn.hip", "mv_decode.hip", "mv_vqa.hip", "mv_lmloss.hip", "mv_optim.hip",
-           "mv_rowops.hip", "mv_retrieval.hip", "mv_report.hip", "mv_vqa_bank.hip", "mv_clf_bank.hip", "mv_batch.hip", "mv_conv.hip", "mv_hostpack.hip", "mv_comm.hip", "mv_api.hip"]      # slowest translation units first
+           "mv_rowops.hip", "mv_retrieval.hip", "mv_report.hip", "mv_vqa_bank.hip", "mv_clf_bank.hip", "mv_bleu.hip", "mv_batch.hip", "mv_conv.hip", "mv_hostpack.hip", "mv_comm.hip", "mv_api.hip"]      # slowest translation units first
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 
 

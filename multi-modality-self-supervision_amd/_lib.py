@@ -114,6 +114,9 @@ PROTOTYPES = {
     # classification from a device-resident bank (csrc/mv_clf_bank.hip)
     "mv_clf_assemble": [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "mv_clf_counts": [vp, i32, vp, i32, vp, i32, i32, vp, vp],
+    # corpus BLEU of generated reports (csrc/mv_bleu.hip)
+    "mv_bleu_words": [vp, i32, i32, i32, vp, vp, vp, i32, i64, i64, i64, vp, vp, vp],
+    "mv_bleu_counts": [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp],
 }
 # include/medvill_debug.h: exported by libmedvill_hip_dbg.so only
 DEBUG_PROTOTYPES = {"mv_debug_set_knob": [i32, i32], "mv_debug_get_knob": [i32]}

@@ -1,7 +1,8 @@
 // What the batch kernels of the device-resident banks share (mv_pair_assemble, mv_report_assemble, mv_vqa_assemble): each launches a
 // grid (samples, chunks) in which every block copies one chunk of its sample's feature row out of the image bank -- the gather all
 // three are HBM-bound on -- and chunk 0 also writes the sample's small outputs.  Here: the copy, the launcher's chunk plan and the
-// pieces of chunk 0 that do not depend on the task.  The text side of each kernel stays in its own file.
+// pieces of chunk 0 that do not depend on the task.  The text side of each kernel stays in its own file.  Also the block sum into a
+// 64-bit counter that the kernels behind the evaluations' metrics share.
 #pragma once
 #include "mv_dispatch.h"
 
@@ -73,6 +74,20 @@ __device__ __forceinline__ void write_desc(int32_t* __restrict__ desc, int i, in
   desc[3 * i + 0] = family;
   desc[3 * i + 1] = N + 2;
   desc[3 * i + 2] = N + 2 + len;
+}
+
+// ---- the counting kernels (mv_clf_counts, mv_bleu_counts)
+// the block's sum of v -> one 64-bit atomic (none for a zero); every lane of the NT calls it, sh holds NT / 64 words
+__device__ __forceinline__ void block_add(unsigned long long v, unsigned long long* __restrict__ dst, unsigned long long* sh) {
+  for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < NT / 64; ++w) t += sh[w];
+    if (t) atomicAdd(dst, t);
+  }
+  __syncthreads();
 }
 
 }  // namespace mv_bank

@@ -82,19 +82,6 @@ __device__ __forceinline__ void list_elem(int z, int C, unsigned e, int& j, int&
   }
 }
 
-// the block's sum of v -> one 64-bit atomic (none for a zero); every lane calls it
-__device__ __forceinline__ void block_add(unsigned long long v, unsigned long long* __restrict__ dst, unsigned long long* sh) {
-  for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int w = 0; w < NT / 64; ++w) t += sh[w];
-    if (t) atomicAdd(dst, t);
-  }
-  __syncthreads();
-}
-
 // grid (tiles of the negative side, splits of the positive side, C + 1 lists).  A block holds TILE elements of its list in registers as
 // negatives (a positive or an element past the list: KEY_NO_NEG), walks its share of the list in rounds of TILE candidates whose positives
 // it packs into LDS, and compares every packed positive (one broadcast read for four) with its RPT registers, branch-free.  The blocks of

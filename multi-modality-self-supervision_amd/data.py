@@ -460,7 +460,10 @@ class ReportBank(DeviceBank):
                                  pipeline per sample with random.choices (:282); that draw stays with the caller.  (key, step) select the
                                  masking draw's random words; `draws` [B, T+1] overrides them (hip_ops.report_assemble).  idx given on the
                                  host is checked against the bank there and the descriptors' host copy comes from the host lengths and
-                                 modes (no read-back); idx on the device (int32) is clamped into the bank by the kernel."""
+                                 modes (no read-back); idx on the device (int32) is clamped into the bank by the kernel.
+      set_vocab(tokens), set_references(texts=None)
+                                 what model.evaluate (report_eval.evaluate: corpus BLEU-1..4 of the generated reports) needs: the word
+                                 tables of the vocabulary and every item's reference words as 64-bit keys on the device."""
 
     def __init__(self, model=None, device=None, feat_dtype=None, max_pred=10, mask_prob=0.15):
         super().__init__(model, device, feat_dtype)
@@ -468,6 +471,57 @@ class ReportBank(DeviceBank):
         if self.max_pred < 1:
             raise ValueError("ReportBank: max_pred >= 1")
         self.n_pred = None
+        self.vocab = self.ref_key = self.ref_n = None
+
+    def set_vocab(self, tokens):
+        """The vocabulary, id -> token string, for the BLEU evaluation: report_eval.word_tables' tables go onto the device; the ids of
+        '[SEP]' and '[PAD]', at which a generated row ends, are looked up by name as the reference does."""
+        from .report_eval import END_TOKENS, word_tables
+        tokens = list(tokens)
+        missing = [t for t in END_TOKENS if t not in tokens]
+        if missing:
+            raise ValueError(f"set_vocab: the vocabulary has no {' / '.join(missing)}")
+        tb = word_tables(tokens)
+        self.vocab = dict(tokens=tokens, size=len(tokens), sep_id=tokens.index(END_TOKENS[0]), pad_id=tokens.index(END_TOKENS[1]),
+                          empty_key=tb["empty_key"], **{k: tb[k].to(self.device) for k in ("tok_key", "tail_key", "tail_pow")})
+        return self
+
+    def set_references(self, texts=None):
+        """The reference words of every item, as padded key rows ref_key int64 [n, W] and counts ref_n int32 [n] on the device.
+        texts: the raw reports (the reference's gt_caption), keyed on the host as text.split(' '); None: the bank's own report rows,
+        through one mv_bleu_words launch (data sets that keep only ids; needs set_vocab).  Refused: a report of more than 1024 words,
+        a count of texts other than the bank's."""
+        from . import hip_ops as ops
+        from .report_eval import text_keys
+        if self.n_texts == 0:
+            raise ValueError("set_references: the bank holds no reports (add_reports)")
+        if texts is None:
+            if self.vocab is None:
+                raise ValueError("set_references(None) words the bank's own rows: set_vocab first")
+            v = self.vocab
+            self.ref_key, self.ref_n = ops.bleu_words(self.txt_ids, v["tok_key"], v["tail_key"], v["tail_pow"], v["sep_id"], v["pad_id"],
+                                                      v["empty_key"])
+            return self
+        texts = list(texts)
+        if len(texts) != self.n_texts:
+            raise ValueError(f"set_references: {len(texts)} texts for a bank of {self.n_texts} reports")
+        keys, counts = text_keys(texts)
+        if keys.shape[1] > ops.BLEU_MAX_WORDS:
+            raise ValueError(f"set_references: a report of {keys.shape[1]} words (at most {ops.BLEU_MAX_WORDS})")
+        self.ref_key, self.ref_n = keys.to(self.device).contiguous(), counts.to(self.device)
+        return self
+
+    def check_eval(self, vocab_size: int):
+        """What report_eval.evaluate needs of the bank: images, a vocabulary of the model's size, a reference per item."""
+        n = self.n_texts
+        if n == 0 or n != self.n_images:
+            raise ValueError(f"the bank holds {n} reports and {self.n_images} images: item i is image i with report i")
+        if self.vocab is None or self.ref_key is None:
+            raise ValueError("the bank has no vocabulary or no references (ReportBank.set_vocab, set_references)")
+        if self.vocab["size"] != int(vocab_size):
+            raise ValueError(f"the bank's vocabulary has {self.vocab['size']} tokens, the model's {int(vocab_size)}")
+        if int(self.ref_key.shape[0]) != n:
+            raise ValueError(f"{int(self.ref_key.shape[0])} references for {n} items: call set_references after the last add_reports")
 
     def add_reports(self, ids, lengths):
         done = self.n_texts

@@ -1142,3 +1142,58 @@ def clf_counts(probs, idx, lab_bits, n_classes, counters=None):
                               L.stream_ptr())
     L.check(rc, f"mv_clf_counts(n={n},C={C})")
     return counters
+
+
+# ---------------------------------------------------------------------------------------------------- corpus BLEU (csrc/mv_bleu.hip)
+BLEU_MAX_WORDS = 1024           # mv_bleu_words / mv_bleu_counts: tokens or words per row (include/medvill.h)
+BLEU_MAX_VOCAB = 1 << 20
+BLEU_MAX_ROWS = 1 << 20
+BLEU_NCOUNT = 10                # num_1..4, den_1..4, hyp_len, ref_len
+
+
+def _bleu_rows(who, key, cnt):
+    if key.dtype != torch.int64 or cnt.dtype != torch.int32:
+        raise TypeError(f"{who}: word keys int64, word counts int32")
+    if key.dim() != 2 or not key.is_contiguous() or cnt.dim() != 1 or cnt.shape[0] != key.shape[0] or not cnt.is_contiguous():
+        raise ValueError(f"{who}: contiguous word keys [rows, words] and one count per row")
+
+
+def bleu_words(ids, tok_key, tail_key, tail_pow, eos_id, pad_id, empty_key):
+    """The word keys of generated rows (see mv_bleu_words): ids int64 [n, T] (rows may be strided), the three int64 [V] tables of
+    report_eval.word_tables -> (word_key int64 [n, T], n_words int32 [n])."""
+    L.require_cuda(ids, tok_key, tail_key, tail_pow)
+    tables = (tok_key, tail_key, tail_pow)
+    if ids.dtype != torch.int64 or any(t.dtype != torch.int64 for t in tables):
+        raise TypeError("bleu_words: ids and the tables are int64")
+    if ids.dim() != 2 or ids.stride(1) != 1 or ids.stride(0) < ids.shape[1]:
+        raise ValueError("bleu_words: ids [n, T] with unit column stride")
+    V = int(tok_key.numel())
+    if any(t.dim() != 1 or t.numel() != V or not t.is_contiguous() for t in tables):
+        raise ValueError("bleu_words: three contiguous tables over one vocabulary")
+    n, T = int(ids.shape[0]), int(ids.shape[1])
+    word_key = torch.empty((n, T), dtype=torch.int64, device=ids.device)
+    n_words = torch.empty(n, dtype=torch.int32, device=ids.device)
+    rc = _lib().mv_bleu_words(L.ptr(ids), int(ids.stride(0)), n, T, L.ptr(tok_key), L.ptr(tail_key), L.ptr(tail_pow), V, int(eos_id),
+                              int(pad_id), int(empty_key), L.ptr(word_key), L.ptr(n_words), L.stream_ptr())
+    L.check(rc, f"mv_bleu_words(n={n},T={T},V={V})")
+    return word_key, n_words
+
+
+def bleu_counts(hyp_key, hyp_n, ref_key, ref_n, idx, counters=None):
+    """The integer counts corpus BLEU-1..4 follow from (see mv_bleu_counts): hypothesis rows [n, Th] / [n], reference rows
+    [n_items, Tr] / [n_items], idx int32 [n] -> counters int64 [10] = {num_1..4, den_1..4, hyp_len, ref_len}; `counters` (on the
+    device) is accumulated into when given."""
+    L.require_cuda(hyp_key, hyp_n, ref_key, ref_n, idx, counters)
+    _bleu_rows("bleu_counts", hyp_key, hyp_n)
+    _bleu_rows("bleu_counts", ref_key, ref_n)
+    n = int(hyp_key.shape[0])
+    if idx.dtype != torch.int32 or idx.dim() != 1 or idx.shape[0] != n or not idx.is_contiguous():
+        raise TypeError("bleu_counts: idx contiguous int32, one per hypothesis row")
+    if counters is None:
+        counters = torch.zeros(BLEU_NCOUNT, dtype=torch.int64, device=hyp_key.device)
+    elif counters.dtype != torch.int64 or counters.numel() != BLEU_NCOUNT or not counters.is_contiguous():
+        raise TypeError(f"bleu_counts: counters int64 [{BLEU_NCOUNT}]")
+    rc = _lib().mv_bleu_counts(L.ptr(hyp_key), int(hyp_key.shape[1]), L.ptr(hyp_n), n, L.ptr(ref_key), int(ref_key.shape[1]), L.ptr(ref_n),
+                               int(ref_key.shape[0]), L.ptr(idx), L.ptr(counters), L.stream_ptr())
+    L.check(rc, f"mv_bleu_counts(n={n})")
+    return counters

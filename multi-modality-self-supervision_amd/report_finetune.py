@@ -24,6 +24,7 @@ from types import SimpleNamespace
 import torch
 
 from . import hip_ops as ops
+from . import report_eval
 from .checkpoint import from_finetune_keys, hf_config, read_pretrained, to_finetune_keys, write_pretrained
 from .cxrbert import run_backward
 from .task import TaskModel, check_single_rank
@@ -247,6 +248,10 @@ class CXRBertForReportFinetune(TaskModel):
     def generate(self, cls_tok, input_img, sep_tok, **kw):
         """CXRBERT.generate of the weights being fine-tuned (validation decoding; eval mode, no gradients, engine state restored)."""
         return self.bert.generate(cls_tok, input_img, sep_tok, **kw)
+
+    def evaluate(self, bank, idx=None, batch_size=64, **generate_kwargs):
+        """Corpus BLEU-1..4 of the reports generated for the items of a data.ReportBank: report_eval.evaluate (DESIGN.md "8u")."""
+        return report_eval.evaluate(self, bank, idx=idx, batch_size=batch_size, **generate_kwargs)
 
     # ------------------------------------------------------------------ state dict (the reference's fine-tune layout)
     def _apply(self, fn, *a, **k):

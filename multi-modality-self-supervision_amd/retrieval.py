@@ -264,4 +264,9 @@ class CXRBertForGeneration(nn.Module):
     def generate(self, cls_tok, input_img, sep_tok, **kw):
         return self.bert.generate(cls_tok, input_img, sep_tok, **kw)
 
+    def evaluate(self, bank, idx=None, batch_size=64, **generate_kwargs):
+        """Corpus BLEU-1..4 of the reports generated for the items of a data.ReportBank: report_eval.evaluate (DESIGN.md "8u")."""
+        from .report_eval import evaluate
+        return evaluate(self, bank, idx=idx, batch_size=batch_size, **generate_kwargs)
+
     forward = generate
