@@ -7,6 +7,7 @@ cross-compiles for gfx950 without a GPU, so this runs in the CPU-only build cont
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -18,8 +19,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libmedvill_hip.so")
 LIB_DBG = os.path.join(HERE, "libmedvill_hip_dbg.so")
-SOURCES = ["mv_gemm_ring_tn.hip", "mv_gemm_ring_tn4.hip", "mv_gemm_ring_nt.hip", "mv_gemm_ring_nn.hip", "mv_gemm_ring_tnn.hip", "mv_gemm.hip", "mv_attn.hip", "mv_decode.hip", "mv_vqa.hip", "mv_lmloss.hip", "mv_optim.hip",
-           "mv_rowops.hip", "mv_retrieval.hip", "mv_report.hip", "mv_vqa_bank.hip", "mv_clf_bank.hip", "mv_bleu.hip", "mv_batch.hip", "mv_conv.hip", "mv_hostpack.hip", "mv_comm.hip", "mv_api.hip"]      # slowest translation units first
+SOURCES = ["mv_gemm_ring_tn.hip", "mv_gemm_ring_tn4.hip", "mv_gemm_ring_nt.hip", "mv_gemm_ring_nn.hip", "mv_gemm_ring_tnn.hip", "mv_gemm.hip", "mv_attn_mfma.hip", "mv_attn_probs.hip", "mv_decode.hip", "mv_vqa.hip", "mv_lmloss.hip", "mv_optim.hip",
+           "mv_rowops.hip", "mv_attn_simple.hip", "mv_attn_mask.hip", "mv_attn.hip", "mv_retrieval.hip", "mv_report.hip", "mv_vqa_bank.hip", "mv_clf_bank.hip", "mv_bleu.hip", "mv_batch.hip", "mv_conv.hip", "mv_hostpack.hip", "mv_comm.hip", "mv_api.hip"]      # slowest translation units first
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 
 
@@ -37,12 +38,15 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def header_deps() -> list:
+    """what every object depends on besides its own source: every header of csrc/ and the C ABI"""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(os.path.dirname(HERE), "include", "medvill.h")]
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "mv_common.h"), os.path.join(CSRC, "mv_gemm_common.h"), os.path.join(CSRC, "mv_gemm_ring.h"), os.path.join(CSRC, "mv_gemm_group.h"), os.path.join(CSRC, "mv_gemm_plan.h"),
-               os.path.join(CSRC, "mv_dispatch.h"), os.path.join(CSRC, "mv_bank.h"),
-               os.path.join(os.path.dirname(HERE), "include", "medvill.h")]
+    headers = header_deps()
     dbg_header = os.path.join(os.path.dirname(HERE), "include", "medvill_debug.h")      # only the debug build of mv_api.hip includes it
     jobs = []
     for s in SOURCES:

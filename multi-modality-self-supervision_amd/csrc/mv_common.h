@@ -47,6 +47,16 @@ __attribute__((visibility("hidden"))) int mv_knob(int id);
     if (e__ != hipSuccess) return (int)e__;         \
   } while (0)
 
+// Launch of a kernel that uses dynamic LDS (the GEMMs and the MFMA attention kernels).  The kernel is a template argument, so every kernel
+// has its own instantiation and with it its own function-local static: hipFuncAttributeMaxDynamicSharedMemorySize is set once per process
+// and kernel.  (Once per process is not once per device -- DESIGN.md; it is this one line now.)
+template <auto KERNEL, typename... Args>
+inline void mv_launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const Args&... args) {
+  static const hipError_t attr_once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  (void)attr_once;
+  hipLaunchKernelGGL(KERNEL, grid, block, (size_t)lds_bytes, stream, args...);
+}
+
 __device__ __forceinline__ float bf2f(bf16_t x) { return (float)x; }
 __device__ __forceinline__ bf16_t f2bf(float x) { return (bf16_t)x; }
 

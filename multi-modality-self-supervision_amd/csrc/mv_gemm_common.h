@@ -440,16 +440,7 @@ __device__ __forceinline__ bf16x8 g2_frag(const char* tile, int base, int l15, i
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-
-// Launch of a kernel that uses dynamic LDS.  The kernel is a template argument, so every kernel has its own instantiation and with it
-// its own function-local static: hipFuncAttributeMaxDynamicSharedMemorySize is set once per process and kernel.  (Once per process is
-// not once per device -- DESIGN.md; it is this one line now.)
-template <auto KERNEL, typename... Args>
-inline void mv_launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const Args&... args) {
-  static const hipError_t attr_once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  (void)attr_once;
-  hipLaunchKernelGGL(KERNEL, grid, block, (size_t)lds_bytes, stream, args...);
-}
+// (mv_launch_lds, the launch of a kernel with dynamic LDS: mv_common.h)
 
 // launchers of the 256-row kernels: one translation unit per operand layout (mv_gemm_ring_{nt,nn,tn,tnn,tn4}.hip; they compile in
 // parallel).  Each switches on plan.kernel and returns MV_E_ARG for a kernel it has no instantiation of; mv_gemm_plan never asks for one.

@@ -2,7 +2,7 @@
 // (data/dataset_origin.py:138-176: 134 MB at B = 64, L = 512).  The trainer derives {family, n2, vl} descriptors from a few probe
 // entries and runs on those (mv_mask_build); to hold the "mask indexing is bit-exact" contract on EVERY batch, every entry of the
 // shipped matrix is compared here with what mv_mask_build makes of the descriptors -- the same predicates as mask_build_kernel
-// (mv_attn.hip), evaluated a 32-column word at a time -- in one pass over the matrix at memory speed, split over
+// (mv_attn_mask.hip), evaluated a 32-column word at a time -- in one pass over the matrix at memory speed, split over
 // host threads by sample.  Nothing crosses PCIe; the trainer runs it on a worker thread one batch ahead of the step.
 #include <stdint.h>
 #include <stddef.h>

@@ -435,7 +435,7 @@ def set_attn_fwd(variant: int = 0):
 
 
 def set_attn_order(order: int = 0):
-    """Attention block order (see att_block in csrc/mv_attn.hip): 0 row block slowest, 1 a pair's row blocks adjacent on one XCD."""
+    """Attention block order (see att_block in csrc/mv_attn.h): 0 row block slowest, 1 a pair's row blocks adjacent on one XCD."""
     L.set_knob("attn_order", order)
 
 

@@ -1,4 +1,4 @@
-"""A/B of the attention kernels' block order (att_block in csrc/mv_attn.hip; knob attn_order of the debug library) in ONE process:
+"""A/B of the attention kernels' block order (att_block in csrc/mv_attn.h; knob attn_order of the debug library) in ONE process:
 order 0 = row block slowest (rounds 3-4), order 1 = the row blocks of a (sample, head) pair adjacent on one XCD (round 5).
 Bench shape B = 64, A = 12, dh = 64, f16 operands, dropout 0.1; interleaved rounds, median of HIP-event times.
 usage: python profiles/tools/attn_order_ab.py [rounds]"""

@@ -1,4 +1,4 @@
-"""Case generators, dispatch restatement, fp64 references, bounds and a torch stand-in of the attention sweep (csrc/mv_attn.hip).
+"""Case generators, dispatch restatement, fp64 references, bounds and a torch stand-in of the attention sweep (csrc/mv_attn*.hip).
 
 Plain module: nothing here touches the GPU or the HIP library.  tests/test_attn_fuzz_gpu.py runs the cases on the device,
 tests/test_attn_cases_cpu.py counts the branches they reach and validates the references and the bounds without a GPU.
@@ -14,6 +14,7 @@ tests/test_attn_cases_cpu.py counts the branches they reach and validates the re
   SAFETY; nothing in them is fitted to a kernel's output.
 """
 import math
+import os
 from collections import Counter
 
 import numpy as np
@@ -21,7 +22,17 @@ import torch
 
 from rowops_cases import BF16, DT, F16, F16_SUBNORMAL_HALF_ULP, F32, U16, U32, f32r, out16_bound, sum_bound  # noqa: F401
 
-# ---- constants of csrc/mv_attn.hip and include/medvill.h (tests/test_attn_cases_cpu.py parses the same numbers from the sources) ----
+# ---- the attention sources: one shared header and five units, read by the CPU census files as ONE text.  mv_attn_probs.hip comes last: its
+# entry point closes the text, as it closed the single file these were split from ----
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "multi-modality-self-supervision_amd", "csrc")
+ATTN_FILES = ("mv_attn.h", "mv_attn_mask.hip", "mv_attn_mfma.hip", "mv_attn_simple.hip", "mv_attn.hip", "mv_attn_probs.hip")
+
+
+def attn_source():
+    return "\n".join(open(os.path.join(CSRC, f)).read() for f in ATTN_FILES)
+
+
+# ---- constants of csrc/mv_attn*.{h,hip} and include/medvill.h (tests/test_attn_cases_cpu.py parses the same numbers from the sources) ----
 FWD_NS, DQ_NS, DKV_NS = 3, 4, 4
 MASK_ADD = -10000.0
 MAX_T = 64                    # mv_mask_pack / mv_mask_build: T = ceil(L / 64) <= 64
@@ -192,7 +203,7 @@ def _ring_name(n):
 
 
 def att_block_map(order, nxb, A, B):
-    """flat block index -> (xb, head, b) as att_block() of mv_attn.hip (grid (nxb, A, B), x fastest)"""
+    """flat block index -> (xb, head, b) as att_block() of mv_attn.h (grid (nxb, A, B), x fastest)"""
     nhb = A * B
     out = []
     for flat in range(nxb * nhb):

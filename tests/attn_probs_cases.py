@@ -1,4 +1,4 @@
-"""Cases, dispatch restatement, bound, grading and a torch stand-in of the attention-probability sweep (mv_attn_probs, csrc/mv_attn.hip).
+"""Cases, dispatch restatement, bound, grading and a torch stand-in of the attention-probability sweep (mv_attn_probs, csrc/mv_attn_probs.hip).
 
 Plain module: nothing here touches the GPU or the HIP library.  It builds on tests/attn_cases.py (generators, masks, inputs, the fp64
 forward reference and its p / pd, _score_err, UOP, SAFETY, G_ROWS) without editing it.  tests/test_attn_probs_sweep_gpu.py runs the cases

@@ -66,6 +66,21 @@ def test_product_library_exports_the_header_and_nothing_else_and_has_no_knobs():
     assert b"debug-knobs" not in _lib.load().mv_build_info()
 
 
+def test_the_build_lists_every_unit_and_depends_on_every_header():
+    """a unit missing from SOURCES is not linked, a header missing from the dependency list leaves stale objects behind"""
+    import glob
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_mv_build", os.path.join(ROOT, "multi-modality-self-supervision_amd", "_build.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    units = {os.path.basename(p) for p in glob.glob(os.path.join(b.CSRC, "*.hip"))}
+    assert len(b.SOURCES) == len(set(b.SOURCES)) and set(b.SOURCES) == units and len(units) >= 26
+    deps = {os.path.abspath(p) for p in b.header_deps()}
+    headers = {os.path.abspath(p) for p in glob.glob(os.path.join(b.CSRC, "*.h"))}
+    assert headers and headers <= deps and os.path.abspath(os.path.join(ROOT, "include", "medvill.h")) in deps
+    assert all(os.path.exists(p) for p in deps)
+
+
 def test_workspace_sizing_functions_are_pure_and_match_the_split_k_choice():
     """mv_gemm_workspace_bytes / mv_workspace_bytes: what a host that is not hip_ops.py needs to size split-K workspaces.
     Pure host arithmetic (no kernel, no device memory): callable here."""

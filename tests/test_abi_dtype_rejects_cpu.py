@@ -75,7 +75,7 @@ CASES = {
     "mv_bce_multilabel": (lambda L, d: L.mv_bce_multilabel(P, 8, P, None, 2, 8, None, P, d, 8, None, 1.0, None, None, None, None),
                           ANY, 3, dtype_error),
     "mv_lm_loss_bwd": (lambda L, d: L.mv_lm_loss_bwd(P, 8, 2, 8, P, P, P, P, 2, 0.0, P, P, P, P, None, P, d, 8, None), ANY, 3, dtype_error),
-    # csrc/mv_attn.hip
+    # csrc/mv_attn.hip, csrc/mv_attn_probs.hip
     "mv_attn_fwd": (lambda L, d: L.mv_attn_fwd(d, P, P, P, P, None, P, 2, 64, 2, 64, 0.0, None, None, 0, None, None), ANY, 3, dtype_error),
     "mv_attn_bwd": (lambda L, d: L.mv_attn_bwd(d, P, P, P, P, P, P, P, P, 2, 64, 2, 64, 0.0, None, None, 0, None, None), ANY, 3, dtype_error),
     "mv_attn_probs": (lambda L, d, od: L.mv_attn_probs(d, P, P, P, P, P, od, 2, 64, 2, 64, 0.0, None, 0, None),       # (dtype, out_dtype)

@@ -1,5 +1,5 @@
 """Census of the attention sweep (CPU).  tests/test_attn_fuzz_gpu.py is only worth its GPU time while its cases reach every tile path
-of csrc/mv_attn.hip; this file counts the paths from the dense masks, checks the constants the restatement relies on against the
+of csrc/mv_attn*.hip; this file counts the paths from the dense masks, checks the constants the restatement relies on against the
 sources, checks each fp64 reference against an independent formulation, and validates the bounds of tests/attn_cases.py with a torch
 stand-in of the tile-wise algorithm: the honest stand-in stays below half of every bound on every case, and six deliberately wrong
 ones each break a bound."""
@@ -17,7 +17,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import attn_cases as C                        # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIP = os.path.join(ROOT, "multi-modality-self-supervision_amd", "csrc", "mv_attn.hip")
 HDR = os.path.join(ROOT, "include", "medvill.h")
 GPU_FILE = os.path.join(ROOT, "tests", "test_attn_fuzz_gpu.py")
 MIN_HITS = 3
@@ -95,7 +94,7 @@ def test_generated_cases_are_inside_the_abi():
 
 
 def test_constants_match_the_sources():
-    src = open(HIP).read()
+    src = C.attn_source()
     for name, val in (("FWD_NS", C.FWD_NS), ("DQ_NS", C.DQ_NS), ("DKV_NS", C.DKV_NS)):
         assert int(re.search(r"#define %s (\d+)" % name, src).group(1)) == val
     assert float(re.search(r"#define MASK_ADD \((-?[\d.]+)f\)", src).group(1)) == C.MASK_ADD

@@ -1,4 +1,4 @@
-"""Sweep of every tile path of the attention kernels (csrc/mv_attn.hip) against fp64 references (GPU).
+"""Sweep of every tile path of the attention kernels (csrc/mv_attn_mfma.hip, mv_attn_simple.hip, mv_attn_mask.hip) against fp64 references (GPU).
 
 The cases, the dispatch restatement, the references and the bounds live in tests/attn_cases.py; tests/test_attn_cases_cpu.py counts
 the paths and validates the bounds without a GPU.  Every case runs: nothing here may drop one.  Every output is pre-filled with NaN and

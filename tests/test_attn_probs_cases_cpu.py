@@ -1,6 +1,6 @@
 """Census of the attention-probability sweep (CPU).  tests/test_attn_probs_sweep_gpu.py is only worth its GPU time while its cases
 reach every branch of mv_attn_probs; this file counts the branches from the dense masks, checks the constants the restatement relies on
-against csrc/mv_attn.hip, shows that the fp64 reference alone passes every assertion of the sweep, and validates the bound of
+against csrc/mv_attn*.{h,hip}, shows that the fp64 reference alone passes every assertion of the sweep, and validates the bound of
 tests/attn_probs_cases.py with a torch stand-in: the honest one stays within the bound on every case, seven deliberately wrong ones
 each break it."""
 import ast
@@ -17,7 +17,6 @@ import attn_cases as C                        # noqa: E402
 import attn_probs_cases as P                  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIP = os.path.join(ROOT, "multi-modality-self-supervision_amd", "csrc", "mv_attn.hip")
 GPU_FILE = os.path.join(ROOT, "tests", "test_attn_probs_sweep_gpu.py")
 MIN_HITS = 3
 
@@ -59,7 +58,7 @@ def test_every_length_family_kind_and_option_is_drawn():
 
 
 def test_constants_match_the_source():
-    src = open(HIP).read()
+    src = C.attn_source()
     body = _entry_body(src)
     assert int(re.search(r"if \(Tt > (\d+)\) return MV_E_SHAPE;", body).group(1)) == P.MAX_T
     assert int(re.search(r"if \(dh != (\d+)\) return MV_E_SHAPE;", body).group(1)) == P.MFMA_DH
@@ -71,7 +70,7 @@ def test_constants_match_the_source():
     assert "for (int tk = wid >> 1; tk < T; tk += 2)" in src                  # key tiles by parity of the wave pair (keypar0 / keypar1)
     assert "const int q0 = tq * 64 + 32 * (wid & 1)" in src and "if (q0 >= L) return;" in src
     assert re.search(r"g_mv_impl == 0\) \{\s*if \(dh != 64\)", body)           # the impl knob routes 16-bit data to the VALU kernel
-    assert "mv_debug" not in body and "MV_KNOB_COUNT = 10" in open(os.path.join(os.path.dirname(HIP), "mv_common.h")).read()   # no new knob
+    assert "mv_debug" not in body and "MV_KNOB_COUNT = 10" in open(os.path.join(C.CSRC, "mv_common.h")).read()   # no new knob
 
 
 def _one(cfg):

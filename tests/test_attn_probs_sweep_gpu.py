@@ -1,4 +1,4 @@
-"""Sweep of every branch of mv_attn_probs (csrc/mv_attn.hip) against the fp64 reference (GPU).
+"""Sweep of every branch of mv_attn_probs (csrc/mv_attn_probs.hip) against the fp64 reference (GPU).
 
 Cases, restated dispatch, reference, bound and grading live in tests/attn_probs_cases.py; tests/test_attn_probs_cases_cpu.py counts the
 branches and validates the bound without a GPU.  Every case runs.  The output sits inside one allocation, pre-filled with NaN, with
