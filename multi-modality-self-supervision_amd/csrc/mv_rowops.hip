@@ -326,9 +326,11 @@ __device__ __forceinline__ void emb_decode(const EmbArgs& a, int b, int l, int& 
   }
   else if (l == a.N + 1) { tok = (int)a.sep_tok[b]; pos = 0; typ = 0; }
   else { const int t = l - a.N - 2; tok = (int)a.txt[(size_t)b * a.T + t]; pos = t; typ = (int)a.segment[(size_t)b * a.T + t]; }
-  // clamp so that a bad id can never fault (HF would raise an index error on the host)
+  // clamps, so that a bad id can never fault (HF would raise an index error on the host): a token id >= V reads row V - 1 and a negative
+  // one row 0; a position outside 0..maxpos-1 and a type outside 0..1 go to the nearer end.  tok == -1 is left to the image rows alone
+  // (reg >= 0, l in 1..N): at [CLS], [SEP] and the text positions it is a negative id like any other.
   if (tok >= a.V) tok = a.V - 1;
-  if (tok < -1) tok = 0;
+  if (reg < 0 && tok < 0) tok = 0;
   pos = pos < 0 ? 0 : (pos >= a.maxpos ? a.maxpos - 1 : pos);
   typ = typ < 0 ? 0 : (typ > 1 ? 1 : typ);
 }
